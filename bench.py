@@ -7,9 +7,16 @@ losses, backward, and the Adam(lr 1e-4, wd 1e-4) update (:116-121), fp32, on a s
 B-sample batch (4 x 256x256 cameras) that is resident in HBM before timing.
 
     python bench.py [--gpus N --steps K --warmup W --batch B] [--precision bf16] [--workload c4]
+                    [--dump-outputs DIR] [--full]
 --precision bf16 is BASELINE configs[2] (C3); --workload c4 is configs[3] (6 cams x 512^2, B=4
 per GPU; its own metric name, no lift-splat / step roofline entries).  The default is the
 metric's configuration, configs[1] (C2).
+A plain run sets up, warms up, times the K steps and prints the result line (samples/s,
+ms_per_step, the step's roofline fraction, the final loss).  --full adds everything that takes
+runs of its own: the conv-family and lift-splat kernel rooflines, the C4 lift-splat pair, the
+CPU-oracle baseline and the secondary C3 / C4 / C5 records (--no-cpu-baseline / --no-secondary
+drop those two legs of a --full run); without it these entries of the line are null.
+--dump-outputs DIR writes what the last timed step produced (dump_outputs) as DIR/<name>.npy.
 N>1: one rank per GPU, RCCL over xGMI.  Under torch.distributed.run (WORLD_SIZE set) the ranks
 are already there; from a plain command line `--gpus N` re-launches this script under
 torch.distributed.run with N ranks before anything touches the GPU.  Each rank runs B samples
@@ -304,6 +311,34 @@ def train_step_rate(dev, world, rank, batch, steps, warmup, hires=False, eager=F
             "loss": loss, "module": mod, "step": step}
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of each flat buffer by --dump-outputs (16 MB as fp32)
+
+
+def dump_outputs(dst, step, loss):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in
+    `dst`: loss.npy (the step's return value, one element), and the two buffers the step
+    leaves behind in the optimizer's flat layout, params_sample.npy (the weights after the
+    Adam update) and grads_sample.npy (the gradients that update read: this rank's own, or the
+    all-reduced sum at N > 1).  Both are the same DUMP_SAMPLE elements, at sorted indices drawn
+    once from a generator seeded with 0 (the buffers hold ~78 MB each), so two builds run
+    with the same arguments write arrays that compare element for element."""
+    import numpy as np
+
+    opt = step.opt
+    grads = step.flat_grad
+    if grads is None:
+        grads = torch.zeros(opt.numel, dtype=torch.float32, device=opt.flat.device)
+        opt.gather_grads(grads)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    idx = torch.randint(opt.numel, (min(DUMP_SAMPLE, opt.numel),), generator=g).sort().values
+    idx = idx.to(opt.flat.device)
+    torch.cuda.synchronize()
+    os.makedirs(dst, exist_ok=True)
+    for name, t in (("loss", loss.detach().reshape(1)), ("params_sample", opt.flat[idx]),
+                    ("grads_sample", grads[idx])):
+        np.save(os.path.join(dst, name + ".npy"), t.float().cpu().numpy())
+
+
 def conv_roofline(step, lowp, n_eager=3, batch=8):
     """The headline roofline entry: the conv GEMM family (forward + data gradient), its FLOPs
     (2*N*Cout*P*Q*Cin*R*S per launch) over its summed HIP-event time in `n_eager` eager
@@ -485,7 +520,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eager", action="store_true", help="no HIP-graph capture of the step")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the C3 / C4 / C5 sub-records of the default (C2, N=1) line")
+                    help="with --full: skip the C3 / C4 / C5 sub-records of the default (C2, N=1) line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the kernel rooflines (conv family, "
+                         "lift-splat, C4 lift-splat pair), the CPU-oracle baseline and the "
+                         "secondary C3 / C4 / C5 records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and a fixed sample of the updated "
+                         "weights and of their gradients to DIR/<name>.npy (float32)")
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32",
                     help="GEMM operands: fp32 (C2, default) or bf16 (C3: bf16 operands in the "
                          "forward, data-gradient and weight-gradient conv GEMMs and transformer "
@@ -536,9 +578,10 @@ def main():
     value, ms_step = r["value"], r["ms_per_step"]
     final_loss = round(float(loss), 4)
     data = step.batch
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step, loss)
 
     lowp = args.precision != "fp32"
-    roofline, kern = conv_roofline(step, lowp, batch=args.batch)
     step_tfs = STEP_GFLOP_PER_SAMPLE * 1e9 * args.batch / (ms_step * 1e-3) / 1e12
     step_roofline = None if hires else {"bound": "mfma", "achieved": round(step_tfs, 2), "peak": FP32_MFMA_PEAK_TFS,
                      "unit": "TFLOP/s", "frac": round(step_tfs / FP32_MFMA_PEAK_TFS, 4),
@@ -546,52 +589,54 @@ def main():
                      "basis": "3 x 29.94 GFLOP forward per sample (SURVEY.md §8d) x B per GPU "
                               "/ ms_per_step"}
 
-    mean_ms, n_fwd = lss_fwd_kernel_ms(mod.parking_model.bev_model._plan, dev)
-    achieved = lss_fwd_bytes(args.batch) / (mean_ms * 1e-3) / 1e9
-    roofline_lss = None if hires else {"kernel": "e2ep::k_lss_fwd (fused depth x feature outer product + pillar "
-                              "pooling, the north-star lift-splat kernel)",
-                    "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                    "traffic": load_traffic(args.batch),
-                    "bytes_per_launch": lss_fwd_bytes(args.batch), "launch_ms": round(mean_ms, 5),
-                    "launches": n_fwd, "timing": "HIP events around back-to-back launches on the "
-                                                 "launch stream, model's pillar plan",
-                    "plan_rebuild_ms": round(plan_rebuild_ms(
-                        mod.parking_model.bev_model, data["intrinsics"], data["extrinsics"], dev), 4),
-                    "plan_note": "the train step reuses the pillar plan memoised on the host K/E "
-                                 "bytes (constant rig); plan_rebuild_ms is the per-step cost if "
-                                 "it were rebuilt (device K/E, the agent path)"}
+    roofline = roofline_lss = c4 = base = secondary = kern = None
+    if args.full:
+        roofline, kern = conv_roofline(step, lowp, batch=args.batch)
 
-    c4 = lss_c4(dev) if rank == 0 else None
+        mean_ms, n_fwd = lss_fwd_kernel_ms(mod.parking_model.bev_model._plan, dev)
+        achieved = lss_fwd_bytes(args.batch) / (mean_ms * 1e-3) / 1e9
+        roofline_lss = None if hires else {"kernel": "e2ep::k_lss_fwd (fused depth x feature outer product + pillar "
+                                  "pooling, the north-star lift-splat kernel)",
+                        "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                        "traffic": load_traffic(args.batch),
+                        "bytes_per_launch": lss_fwd_bytes(args.batch), "launch_ms": round(mean_ms, 5),
+                        "launches": n_fwd, "timing": "HIP events around back-to-back launches on the "
+                                                     "launch stream, model's pillar plan",
+                        "plan_rebuild_ms": round(plan_rebuild_ms(
+                            mod.parking_model.bev_model, data["intrinsics"], data["extrinsics"], dev), 4),
+                        "plan_note": "the train step reuses the pillar plan memoised on the host K/E "
+                                     "bytes (constant rig); plan_rebuild_ms is the per-step cost if "
+                                     "it were rebuilt (device K/E, the agent path)"}
 
-    base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        threads, cpu_model = host_cores()
-        # C4 CPU steps take ~4x a C2 one: a bounded sample of B=1 steps (samples/s is per sample)
-        cb = 1 if hires else args.batch
-        cs, cw = (3, 1) if hires else (args.cpu_steps, args.cpu_warmup)
-        v, med, ts = cpu_baseline(cb, cs, cw, threads, hires)
-        base = {"value": round(v, 4), "unit": "samples/s", "cores": threads, "kind": "port",
-                "cpu_model": cpu_model,
-                "sample": f"median of {cs} timed train steps (after {cw} warm-up) of the oracle CPU "
-                          f"restatement at B={cb}, {'6x512^2' if hires else '4x256^2'}, fp32, "
-                          f"{threads} threads; step times "
-                          + ", ".join(f"{t:.2f}" for t in ts) + " s"}
+        c4 = lss_c4(dev) if rank == 0 else None
 
-    secondary = None
-    if (rank == 0 and world == 1 and not hires and not lowp and not args.eager
-            and not args.no_secondary):
-        # the other BASELINE configs on this GPU, each on a fresh model (the C2 graphs freed)
-        mod = step = r = data = loss = None
-        _release()
-        secondary = {}
-        threads = host_cores()[0]
-        for name, fn in (("c3", lambda: secondary_c3(dev, args.steps, args.warmup)),
-                         ("c4", lambda: secondary_c4(dev, max(5, args.steps // 2), 3)),
-                         ("c5", lambda: secondary_c5(dev, cpu_iters=0 if args.no_cpu_baseline
-                                                     else 5, cpu_threads=threads))):
-            secondary[name] = fn()
-            print(f"[bench] {name}: {secondary[name]}", file=sys.stderr, flush=True)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            threads, cpu_model = host_cores()
+            # C4 CPU steps take ~4x a C2 one: a bounded sample of B=1 steps (samples/s is per sample)
+            cb = 1 if hires else args.batch
+            cs, cw = (3, 1) if hires else (args.cpu_steps, args.cpu_warmup)
+            v, med, ts = cpu_baseline(cb, cs, cw, threads, hires)
+            base = {"value": round(v, 4), "unit": "samples/s", "cores": threads, "kind": "port",
+                    "cpu_model": cpu_model,
+                    "sample": f"median of {cs} timed train steps (after {cw} warm-up) of the oracle CPU "
+                              f"restatement at B={cb}, {'6x512^2' if hires else '4x256^2'}, fp32, "
+                              f"{threads} threads; step times "
+                              + ", ".join(f"{t:.2f}" for t in ts) + " s"}
+
+        if (rank == 0 and world == 1 and not hires and not lowp and not args.eager
+                and not args.no_secondary):
+            # the other BASELINE configs on this GPU, each on a fresh model (the C2 graphs freed)
+            mod = step = r = data = loss = None
+            _release()
+            secondary = {}
+            threads = host_cores()[0]
+            for name, fn in (("c3", lambda: secondary_c3(dev, args.steps, args.warmup)),
+                             ("c4", lambda: secondary_c4(dev, max(5, args.steps // 2), 3)),
+                             ("c5", lambda: secondary_c5(dev, cpu_iters=0 if args.no_cpu_baseline
+                                                         else 5, cpu_threads=threads))):
+                secondary[name] = fn()
+                print(f"[bench] {name}: {secondary[name]}", file=sys.stderr, flush=True)
 
     if rank == 0:
         line = {"metric": METRIC_C4 if hires else METRIC, "value": round(value, 3), "unit": "samples/s", "n_gpus": world,
@@ -614,8 +659,9 @@ def main():
                 "lss_c4": c4, "cpu_baseline": base, "final_loss": final_loss,
                 "secondary": secondary}
         print(json.dumps(line), flush=True)
-        print("kernel timing (launches, mean ms, total ms):",
-              {k: (n, round(m, 4), round(t, 3)) for k, (n, m, t) in kern.items()}, file=sys.stderr)
+        if kern is not None:
+            print("kernel timing (launches, mean ms, total ms):",
+                  {k: (n, round(m, 4), round(t, 3)) for k, (n, m, t) in kern.items()}, file=sys.stderr)
     if world > 1:
         dist.destroy_process_group()
 

@@ -4,14 +4,15 @@
 # Steps run in order, each under its own time limit, and the script stops at the first failure:
 #   tests[:FILES]     GPU tests (all of tests/, or the comma-separated files)
 #   smoke             __graft_entry__.smoke()
-#   bench             the default bench line (C2 + secondary C3 / C4 / C5 + cpu_baseline)
+#   bench             the full bench line (bench.py --full: C2 + kernel rooflines + secondary
+#                     C3 / C4 / C5 + cpu_baseline)
 #   c2 | c3           one bench line, no CPU baseline / secondaries (c3: --precision bf16)
 #   ab:VAR:REP:v1,v2  interleaved in-step A/B of an environment switch on C2 (c3ab: on C3);
 #                     values separated by '/' when they contain commas, by '|' when they
 #                     contain '/' (library paths for E2EP_LIB)
 #   table:PREC        rocprofv3 kernel trace of 10 replayed steps (PREC fp32 | bf16) ->
 #                     step_kernels_PREC.txt + step_sequence_PREC.txt
-#   stats             rocprofv3 --kernel-trace --stats of the default bench command
+#   stats             rocprofv3 --kernel-trace --stats of the full bench command
 #   cmd:SHELL         an extra command (e.g. a scripts/*.py micro-benchmark), 600 s limit
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 export TMPDIR=/tmp
@@ -29,7 +30,7 @@ for st in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
       tail -1 "$O/smoke.log" ;;
     bench)
-      timeout -k 10 400 python bench.py > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
+      timeout -k 10 400 python bench.py --full > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
       echo "bench $(val value "$O/bench.log") $(val ms_per_step "$O/bench.log")" ;;
     c2|c3)
       p=""; [ "$st" = c3 ] && p="--precision bf16"
@@ -57,7 +58,7 @@ for st in "$@"; do
       tail -1 "$O/step_sequence_$prec.txt"; head -1 "$O/step_kernels_$prec.txt" ;;
     stats)
       d=$O/prof_bench
-      timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -o run -- python3 bench.py > "$d.log" 2>&1 || { tail -20 "$d.log"; exit 1; }
+      timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -o run -- python3 bench.py --full > "$d.log" 2>&1 || { tail -20 "$d.log"; exit 1; }
       find "$d" -name "*kernel_stats.csv" -exec cp {} "$O/bench_kernel_stats.csv" \;
       rm -f $(find "$d" -name "*.db") $(find "$d" -name "*kernel_trace.csv") ;;
     cmd:*)
