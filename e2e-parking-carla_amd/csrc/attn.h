@@ -27,5 +27,10 @@ void attn_mf_fwd(const float *q, const float *k, const float *v, const int *seed
 bool attn_mf_bwd(const float *q, const float *k, const float *v, const float *o,
                  const float *dout, const float *lse2, const int *seed, const AttnDims &a,
                  float *dq, float *dk, float *dv, float *Dbuf, int part, hipStream_t s);
+// attention probabilities P = exp2(S - lse2) of the attn_mf_ok shapes: w [B][H][Sq][Sk], or the
+// head mean [B][Sq][Sk] with average (heads summed in ascending order).  S is the forward
+// kernel's own MFMA chain, so P is the matrix that forward normalised.
+void attn_mf_weights(const float *q, const float *k, const float *lse2, const AttnDims &a,
+                     int average, float *w, hipStream_t s);
 
 }  // namespace e2ep

@@ -24,6 +24,9 @@
 //   k_attn_bwd_kv block = (64-key tile, b*h); Q, dO, lse, D of the head staged in LDS;
 //                 lane = key (k, v, dk, dv rows in registers), 4 waves split the queries;
 //                 dV = P_drop^T dO, dK = scale dS^T Q.
+//   k_attn_w      the attention weights P = exp2(S - lse) for a caller that wants them
+//                 (e2ep_attn_weights), a separate launch after the forward: thread = key,
+//                 query tile broadcast from LDS, rows of P stored contiguously.
 // Dropout: keep(b*h, i, j) = hash(seed, (bh*Sq + i)*Sk + j) >= p, scaled by 1/(1-p); the
 // seed is read from device memory (drawn by the caller each call, graph-capturable), so the
 // backward regenerates the same mask without storing it.
@@ -410,6 +413,64 @@ __global__ void __launch_bounds__(ATT_WAVES * 64) k_attn_bwd_kv(
   }
 }
 
+// Attention weights W[b][h][i][j] = P_ij = exp2(s_ij - lse2_i), recomputed from Q, K and the
+// forward's lse (a separate launch: a call that wants no weights runs none of this).
+// block = (query tile, b*h), thread = key j (Sk <= 256 = the block): the key's row sits in
+// registers, the tile's Q rows, scaled as the forward scales them, are LDS broadcasts, and
+// s_ij is the forward's own fma chain.  A wave's store is 64 consecutive keys of one row.
+// Masked entries are exactly 0; a fully masked row has lse2 = +inf, so it is a row of zeros.
+// AVG: block = (query tile, b), the heads looped in ascending order into registers and scaled
+// by 1/H (no atomics: the same bits every run); smaller tiles, so B = 1 still fills 32 blocks.
+constexpr int ATT_W_QT = 16, ATT_W_QT_AVG = 8;  // queries per block
+template <int DHP, bool AVG>
+__global__ void __launch_bounds__(ATT_WAVES * 64) k_attn_w(
+    const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ lse2,
+    const uint8_t *__restrict__ kpad, AttnDims a, float *__restrict__ wout) {
+  constexpr int QT = AVG ? ATT_W_QT_AVG : ATT_W_QT;
+  __shared__ __attribute__((aligned(16))) float sQ[QT * DHP];
+  __shared__ float slse[QT];
+  const int q0 = blockIdx.x * QT, nr = min(QT, a.Sq - q0);
+  const int j = threadIdx.x, jc = min(j, a.Sk - 1);
+  const int b = AVG ? (int)blockIdx.y : (int)blockIdx.y / a.H;
+  const int h0 = AVG ? 0 : (int)blockIdx.y - b * a.H, h1 = AVG ? a.H : h0 + 1;
+  const bool kmasked = kpad && kpad[(long long)b * a.Sk + jc];
+  const float qmul = a.scale * LOG2E;
+  float acc[QT];
+#pragma unroll
+  for (int r = 0; r < QT; ++r) acc[r] = 0.f;
+  for (int h = h0; h < h1; ++h) {
+    const int bh = b * a.H + h;
+    if (h > h0) __syncthreads();  // the previous head's rows are consumed
+    stage_rows<DHP>(sQ, q + (long long)b * a.q_sb + h * a.dh + (long long)q0 * a.q_ss, nr, a.q_ss,
+                    a.dh);
+    if (j < nr) slse[j] = lse2[(long long)bh * a.Sq + q0 + j];
+    float kr[DHP];
+    load_row<DHP>(kr, k + (long long)b * a.kv_sb + h * a.dh + (long long)jc * a.kv_ss, a.dh, 1.f);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nr * DHP; e += ATT_WAVES * 64) sQ[e] *= qmul;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < QT; ++r) {
+      if (r < nr) {
+        const int i = q0 + r;
+        const float s = dot_lds<DHP>(kr, sQ + r * DHP);
+        const bool masked = kmasked || (a.causal && j > i);
+        const float p = masked ? 0.f : att_exp2(s - slse[r]);
+        if (AVG)
+          acc[r] += p;
+        else if (j < a.Sk)
+          wout[((long long)bh * a.Sq + i) * a.Sk + j] = p;
+      }
+    }
+  }
+  if (AVG) {
+    const float inv_h = 1.f / (float)a.H;
+#pragma unroll
+    for (int r = 0; r < QT; ++r)
+      if (r < nr && j < a.Sk) wout[((long long)b * a.Sq + q0 + r) * a.Sk + j] = acc[r] * inv_h;
+  }
+}
+
 // keep mask as bytes [BH][Sq][Sk] (test/diagnostic entry)
 __global__ void k_attn_keep_mask(const int *seed, int BH, int Sq, int Sk, float p, uint8_t *out) {
   const long long n = (long long)BH * Sq * Sk;
@@ -539,6 +600,31 @@ int e2ep_attn_fwd(const float *q, const float *k, const float *v, int B, int H, 
   }
 #undef E2EP_ATT_FWD
   return launch_status("e2ep_attn_fwd");
+}
+
+int e2ep_attn_weights(const float *q, const float *k, const float *lse, int B, int H, int Sq,
+                      int Sk, int dh, int q_ss, int q_sb, int kv_ss, int kv_sb, float scale,
+                      int causal, const uint8_t *key_pad, int average, float *w, void *stream) {
+  const AttnDims a = make_dims(B, H, Sq, Sk, dh, q_ss, q_sb, kv_ss, kv_sb, 0, 0, scale, causal, 0.f);
+  if (int rc = attn_check(a, "e2ep_attn_weights")) return rc;
+  E2EP_REQUIRE(q && k && lse && w, E2EP_EINVAL, "e2ep_attn_weights: null q / k / lse / w");
+  E2EP_REQUIRE(average == 0 || average == 1, E2EP_EINVAL, "e2ep_attn_weights: average must be 0 or 1");
+  hipStream_t st = as_stream(stream);
+  if (attn_mf_ok(a, key_pad)) {  // the fusion encoder's shape (attn_mf.hip)
+    attn_mf_weights(q, k, lse, a, average, w, st);
+    return launch_status("e2ep_attn_weights");
+  }
+  const dim3 blk(ATT_WAVES * 64);
+  const dim3 grid = average ? dim3(cdiv(Sq, ATT_W_QT_AVG), B) : dim3(cdiv(Sq, ATT_W_QT), B * H);
+#define E2EP_ATT_W(DHP, AVG) \
+  hipLaunchKernelGGL((k_attn_w<DHP, AVG>), grid, blk, 0, st, q, k, lse, key_pad, a, w)
+  if (dh <= 44) {
+    if (average) E2EP_ATT_W(44, true); else E2EP_ATT_W(44, false);
+  } else {
+    if (average) E2EP_ATT_W(64, true); else E2EP_ATT_W(64, false);
+  }
+#undef E2EP_ATT_W
+  return launch_status("e2ep_attn_weights");
 }
 
 size_t e2ep_attn_bwd_workspace(int B, int H, int Sq) { return (size_t)B * H * Sq * sizeof(float); }

@@ -22,6 +22,8 @@
 //                   for the dk / dv pass)
 //   k_attn_bkv_mf   block = (32 keys, b*h), waves split the queries: the transposed tiles
 //                   S^T = K Q^T and dP^T = V dO^T, dV = drop(P)^T dO, dK = scale dS^T Q
+//   k_attn_w_mf     one wave per 32 x 32 tile of the attention weights P = exp2(S - lse2)
+//                   (e2ep_attn_weights), S by the forward's staging and MFMA order
 // Dropout: keep(bh, i, j) = att_keep(seedmix, (bh*Sq + i)*Sk + j, p) (dropout.h), the counter
 // space of attn.hip, so masks, lse and D are interchangeable between the two kernel families.
 #include "attn.h"
@@ -357,6 +359,70 @@ __global__ void __launch_bounds__(256) k_attn_bkv_mf(
     dv[off] = gvs;
     dk[off] = gks * a.scale;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// attention weights (the probabilities themselves, for a caller that displays them)
+// ------------------------------------------------------------------------------------------
+// One wave per 32 x 32 tile of P: S = Q K^T by the forward's staging and MFMA order (so S is
+// bitwise the forward's), P = exp2(S - lse2).  block = (32 queries x 128 keys, b*h), the 4
+// waves on 4 consecutive key tiles; in the C/D layout register r of a lane half is 32
+// consecutive keys of query row mf_row(r, lh), so each store instruction writes two 128-B runs.
+// AVG: block = (32 queries x 128 keys, b), the heads looped in ascending order into a
+// register tile and scaled by 1/H (no atomics: the same bits every run).
+template <bool AVG>
+__global__ void __launch_bounds__(256) k_attn_w_mf(const float *__restrict__ q,
+                                                   const float *__restrict__ k,
+                                                   const float *__restrict__ lse2, AttnDims a,
+                                                   float *__restrict__ wout) {
+  __shared__ float sR[4][32 * MF_RS];  // per-wave row staging
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+  const int nkb = a.Sk / 128;  // 128-key blocks per query tile
+  const int q0 = ((int)blockIdx.x / nkb) * 32;
+  const int j0 = ((int)blockIdx.x % nkb) * 128 + 32 * w;
+  const int b = AVG ? (int)blockIdx.y : (int)blockIdx.y / a.H;
+  const int h0 = AVG ? 0 : (int)blockIdx.y - b * a.H, h1 = AVG ? a.H : h0 + 1;
+  float *stg = sR[w];
+  mf16 acc = mf16{0};
+  for (int h = h0; h < h1; ++h) {
+    const int bh = b * a.H + h;
+    const long long qoff = (long long)b * a.q_sb + h * a.dh;
+    const long long kvoff = (long long)b * a.kv_sb + h * a.dh;
+    float qa[MF_T], kb[MF_T];
+    mf_stage32(stg, q + qoff + (long long)q0 * a.q_ss, a.q_ss, a.dh, a.scale * MF_LOG2E, lane);
+    mf_half_lds(qa, stg, li, lh);
+    mf_stage32(stg, k + kvoff + (long long)j0 * a.kv_ss, a.kv_ss, a.dh, 1.f, lane);
+    mf_half_lds(kb, stg, li, lh);
+    mf16 s = mf16{0};
+#pragma unroll
+    for (int t = 0; t < MF_T; ++t) s = mf_mma(qa[t], kb[t], s);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const long long row = (long long)bh * a.Sq + q0 + mf_row(r, lh);
+      const float p = __builtin_amdgcn_exp2f(s[r] - lse2[row]);
+      if (AVG)
+        acc[r] += p;
+      else
+        wout[row * a.Sk + j0 + li] = p;
+    }
+  }
+  if (AVG) {
+    const float inv_h = 1.f / (float)a.H;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const long long row = (long long)b * a.Sq + q0 + mf_row(r, lh);
+      wout[row * a.Sk + j0 + li] = acc[r] * inv_h;
+    }
+  }
+}
+
+void attn_mf_weights(const float *q, const float *k, const float *lse2, const AttnDims &a,
+                     int average, float *w, hipStream_t s) {
+  const int tiles = (a.Sq / 32) * (a.Sk / 128);
+  if (average)
+    hipLaunchKernelGGL(k_attn_w_mf<true>, dim3(tiles, a.B), dim3(256), 0, s, q, k, lse2, a, w);
+  else
+    hipLaunchKernelGGL(k_attn_w_mf<false>, dim3(tiles, a.B * a.H), dim3(256), 0, s, q, k, lse2, a, w);
 }
 
 bool attn_mf_ok(const AttnDims &a, const uint8_t *key_pad) {

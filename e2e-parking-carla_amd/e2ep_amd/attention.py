@@ -1,22 +1,31 @@
-"""torch.nn.MultiheadAttention forward (need_weights=False) on the fused e2ep attention core.
+"""torch.nn.MultiheadAttention forward on the fused e2ep attention core, with or without the
+attention weights.
 
 The reference's transformer layers call `self_attn(x, x, x, ...)` / `multihead_attn(x, mem,
 mem)` (torch TransformerEncoderLayer / TransformerDecoderLayer, model/feature_fusion.py:13-14,
-model/control_predict.py:19-20).  Here the in-projection stays one hipBLASLt GEMM (packed
+model/control_predict.py:19-20).  Here the in-projection stays one e2ep_gemm launch (packed
 Q|K|V for self-attention, Q and K|V for cross-attention), the attention core runs as
 e2ep_attn_fwd / e2ep_attn_bwd reading Q/K/V in place from that output (no head split
 copies, scores never written), and the out-projection is the module's own linear.
 
-`mha(mod, ...)` falls back to calling the module itself whenever the fused path would not be
-the same computation or would bypass something a caller installed: forward hooks or an
+`mha(mod, ...)` calls the module itself whenever the fused path would not be the same
+computation or would bypass something a caller installed: forward hooks or an
 instance-patched forward (the closed-loop agent's attention capture,
 agent/parking_agent.py:71-80,266-268), a float attn_mask not declared causal, bias_k /
 add_zero_attn, separate projection weights, or shapes outside the kernel's range.
+
+The model's attention modules are `MultiheadAttention` below (model/feature_fusion.py,
+model/control_predict.py retarget the class of the modules torch built), whose own forward
+runs the same fused path and returns the attention weights from e2ep_attn_weights when asked:
+the agent's patch (need_weights=True, average_attn_weights=False) and hook then stay on the
+e2ep kernels.  Where autograd records the call, with dropout active, or with a mask the core
+does not take, that forward is torch's.
 """
 import math
 import os
 
 import torch
+from torch import nn
 
 from . import _lib, conv, nn_ops, rng, timing
 
@@ -26,8 +35,57 @@ from . import _lib, conv, nn_ops, rng, timing
 # extra D launch is on the critical path.
 _SPLIT_BWD = os.environ.get("E2EP_ATTN_SPLIT", "0") == "1"
 
+# E2EP_ATTN_WEIGHTS=0: MultiheadAttention.forward always defers to torch's (A/B timing of the
+# hooked predict against the stock module: scripts/bench_attn_weights.py)
+_FUSED_FORWARD = [os.environ.get("E2EP_ATTN_WEIGHTS", "1") != "0"]
+
 MAX_SEQ = 256
 MAX_HEAD_DIM = 64
+
+
+def _forward(qb, kvb, H, causal, key_pad, p, seed, batch_first):
+    """e2ep_attn_fwd on contiguous operands (see _Attn): (o, lse, (packed, dims, E, k_off,
+    causal, p)), dims = (B, H, Sq, Sk, dh) and the (sequence, batch) strides of Q, K|V and O."""
+    packed = kvb is None
+    kvt = qb if packed else kvb
+    if batch_first:
+        B, Sq, Wq = qb.shape
+        _, Sk, Wkv = kvt.shape
+    else:
+        Sq, B, Wq = qb.shape
+        Sk, _, Wkv = kvt.shape
+    E = Wq // 3 if packed else Wq
+    dh = E // H
+    k_off = E if packed else 0
+    oshape = (B, Sq, E) if batch_first else (Sq, B, E)
+    o = torch.empty(oshape, dtype=qb.dtype, device=qb.device)
+    lse = torch.empty(B * H, Sq, dtype=torch.float32, device=qb.device)
+    kptr = kvt.data_ptr() + 4 * k_off
+    vptr = kptr + 4 * E
+    if batch_first:  # (sequence, batch) strides
+        dims = (B, H, Sq, Sk, dh, Wq, Sq * Wq, Wkv, Sk * Wkv, E, Sq * E)
+    else:
+        dims = (B, H, Sq, Sk, dh, B * Wq, Wq, B * Wkv, Wkv, B * E, E)
+    with timing.region("attn_fwd"):
+        _lib.call("e2ep_attn_fwd", _lib.ptr(qb), kptr, vptr, *dims, 1.0 / math.sqrt(dh),
+                  int(causal), _lib.ptr(key_pad), float(p), _lib.ptr(seed), _lib.ptr(o),
+                  _lib.ptr(lse), _lib.stream())
+    return o, lse, (packed, dims, E, k_off, causal, float(p))
+
+
+def _weights(qb, kvb, lse, cfg, key_pad, average):
+    """e2ep_attn_weights for the forward that returned (lse, cfg): (B, H, Sq, Sk) fp32, or the
+    head mean (B, Sq, Sk)."""
+    packed, dims, _, k_off, causal, _ = cfg
+    B, H, Sq, Sk, dh = dims[:5]
+    kvt = qb if packed else kvb
+    w = torch.empty((B, Sq, Sk) if average else (B, H, Sq, Sk), dtype=torch.float32,
+                    device=qb.device)
+    with timing.region("attn_weights"):
+        _lib.call("e2ep_attn_weights", _lib.ptr(qb), kvt.data_ptr() + 4 * k_off, _lib.ptr(lse),
+                  *dims[:9], 1.0 / math.sqrt(dh), int(causal), _lib.ptr(key_pad), int(average),
+                  _lib.ptr(w), _lib.stream())
+    return w
 
 
 class _Attn(torch.autograd.Function):
@@ -40,32 +98,9 @@ class _Attn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qb, kvb, H, causal, key_pad, p, seed, batch_first=False):
-        packed = kvb is None
-        kvt = qb if packed else kvb
-        if batch_first:
-            B, Sq, Wq = qb.shape
-            _, Sk, Wkv = kvt.shape
-        else:
-            Sq, B, Wq = qb.shape
-            Sk, _, Wkv = kvt.shape
-        E = Wq // 3 if packed else Wq
-        dh = E // H
-        k_off = E if packed else 0
-        oshape = (B, Sq, E) if batch_first else (Sq, B, E)
-        o = torch.empty(oshape, dtype=qb.dtype, device=qb.device)
-        lse = torch.empty(B * H, Sq, dtype=torch.float32, device=qb.device)
-        kptr = kvt.data_ptr() + 4 * k_off
-        vptr = kptr + 4 * E
-        if batch_first:  # (sequence, batch) strides
-            dims = (B, H, Sq, Sk, dh, Wq, Sq * Wq, Wkv, Sk * Wkv, E, Sq * E)
-        else:
-            dims = (B, H, Sq, Sk, dh, B * Wq, Wq, B * Wkv, Wkv, B * E, E)
-        with timing.region("attn_fwd"):
-            _lib.call("e2ep_attn_fwd", _lib.ptr(qb), kptr, vptr, *dims, 1.0 / math.sqrt(dh),
-                      int(causal), _lib.ptr(key_pad), float(p), _lib.ptr(seed), _lib.ptr(o),
-                      _lib.ptr(lse), _lib.stream())
+        o, lse, cfg = _forward(qb, kvb, H, causal, key_pad, p, seed, batch_first)
         ctx.save_for_backward(qb, kvb, o, lse, key_pad, seed)
-        ctx.cfg = (packed, dims, E, k_off, causal, float(p))
+        ctx.cfg = cfg
         return o
 
     @staticmethod
@@ -103,10 +138,16 @@ class _Attn(torch.autograd.Function):
         return dqb, dkvb, None, None, None, None, None, None
 
 
-def attention(qb, kvb, H, causal=False, key_pad=None, p=0.0, seed=None, batch_first=False):
+def attention(qb, kvb, H, causal=False, key_pad=None, p=0.0, seed=None, batch_first=False,
+              need_weights=False, average=True):
     """Functional entry: see _Attn.  key_pad: bool (B, Sk) or None; seed: int32 (1,) device
     tensor, drawn here when p > 0 and none is given; batch_first: (B, S, .) operands and
-    output instead of (S, B, .)."""
+    output instead of (S, B, .).
+
+    need_weights=True returns (o, w): w the softmax probabilities before dropout, (B, H, Sq, Sk)
+    or, with average, their head mean (B, Sq, Sk); masked entries and fully masked rows are 0.
+    That call is not recorded by autograd (neither o nor w carries a gradient): it is for
+    inference, where MultiheadAttention.forward below uses it."""
     if p > 0.0 and seed is None:
         seed = rng.seed(qb.device)
     qb = qb.contiguous()
@@ -115,13 +156,16 @@ def attention(qb, kvb, H, causal=False, key_pad=None, p=0.0, seed=None, batch_fi
         key_pad = key_pad.contiguous()
         if key_pad.dtype != torch.bool:
             raise TypeError("key_pad must be a bool mask (True = ignore key)")
+    if need_weights:
+        qb, kvb = qb.detach(), None if kvb is None else kvb.detach()
+        o, lse, cfg = _forward(qb, kvb, H, bool(causal), key_pad, float(p), seed, bool(batch_first))
+        return o, _weights(qb, kvb, lse, cfg, key_pad, bool(average))
     return _Attn.apply(qb, kvb, H, bool(causal), key_pad, float(p), seed, bool(batch_first))
 
 
-def _fusable(mod, query, key, attn_mask, key_padding_mask, is_causal, batch_first=False):
+def _core_fusable(mod, query, key, attn_mask, key_padding_mask, is_causal, batch_first=False):
+    """Whether the fused core computes this call of a seq-first module (hooks aside)."""
     if key_padding_mask is not None and key_padding_mask.dtype != torch.bool:
-        return False
-    if mod._forward_hooks or mod._forward_pre_hooks or "forward" in mod.__dict__:
         return False
     if not mod._qkv_same_embed_dim or mod.batch_first or mod.bias_k is not None or mod.add_zero_attn:
         return False
@@ -132,6 +176,12 @@ def _fusable(mod, query, key, attn_mask, key_padding_mask, is_causal, batch_firs
     E, H = mod.embed_dim, mod.num_heads
     sd = 1 if batch_first else 0  # sequence dim
     return (E // H <= MAX_HEAD_DIM and query.shape[sd] <= MAX_SEQ and key.shape[sd] <= MAX_SEQ)
+
+
+def _fusable(mod, query, key, attn_mask, key_padding_mask, is_causal, batch_first=False):
+    if mod._forward_hooks or mod._forward_pre_hooks or "forward" in mod.__dict__:
+        return False
+    return _core_fusable(mod, query, key, attn_mask, key_padding_mask, is_causal, batch_first)
 
 
 def mha(mod, query, key, value, attn_mask=None, key_padding_mask=None, is_causal=False,
@@ -174,3 +224,86 @@ def mha(mod, query, key, value, attn_mask=None, key_padding_mask=None, is_causal
         o = attention(q, kv, H, is_causal, key_padding_mask, p, batch_first=batch_first)
     out = nn_ops.linear(o, mod.out_proj.weight, mod.out_proj.bias)
     return ret(out, qs, ks)
+
+
+def _same(a, b):
+    """a and b are one tensor, or views of the same elements (mha's fallback call hands the
+    module three separate transposed views of one activation)."""
+    return a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape
+                      and a.stride() == b.stride() and a.dtype == b.dtype)
+
+
+class MultiheadAttention(nn.MultiheadAttention):
+    """nn.MultiheadAttention (no parameter, buffer or state of its own: an existing module
+    becomes one by `mod.__class__ = MultiheadAttention`) whose forward runs on the e2ep
+    kernels, attention weights included: in-projection (e2ep_gemm), e2ep_attn_fwd,
+    e2ep_attn_weights when need_weights, out-projection.  So a caller that patches the module's
+    forward to ask for the weights and hooks its output (agent/parking_agent.py:71-91) stays on
+    the fused path.
+
+    Taken when the fused core computes the call (_core_fusable: seq-first fp32 HIP operands,
+    key is value, no mask beyond key padding and a declared-causal attn_mask), the effective
+    dropout is 0 and autograd records nothing (grad mode off, or no operand or parameter
+    requires grad); every other call is torch's forward, unchanged.  A fully masked row gives
+    zero weights here where torch gives NaN (known difference)."""
+
+    def _fused(self, query, key, value, key_padding_mask, attn_mask, is_causal):
+        if not _FUSED_FORWARD[0] or not (torch.is_tensor(key) and torch.is_tensor(value)):
+            return False
+        if not _core_fusable(self, query, key, attn_mask, key_padding_mask, is_causal):
+            return False
+        if not _same(key, value) or key.dim() != 3 or key.dtype != query.dtype or not key.is_cuda:
+            return False
+        if key.shape[1] != query.shape[1] or key.shape[2] != query.shape[2]:
+            return False
+        if key_padding_mask is not None and tuple(key_padding_mask.shape) != (key.shape[1], key.shape[0]):
+            return False
+        if attn_mask is not None and tuple(attn_mask.shape) != (query.shape[0], key.shape[0]):
+            return False
+        if is_causal and attn_mask is None:  # torch rejects the hint without its mask
+            return False
+        if self.training and self.dropout > 0.0:
+            return False
+        if torch.is_grad_enabled() and any(
+                t is not None and t.requires_grad
+                for t in (query, key, value, self.in_proj_weight, self.in_proj_bias,
+                          self.out_proj.weight, self.out_proj.bias)):
+            return False
+        return True
+
+    def forward(self, query, key, value, key_padding_mask=None, need_weights=True, attn_mask=None,
+                average_attn_weights=True, is_causal=False):
+        if not self._fused(query, key, value, key_padding_mask, attn_mask, is_causal):
+            return super().forward(query, key, value, key_padding_mask=key_padding_mask,
+                                   need_weights=need_weights, attn_mask=attn_mask,
+                                   average_attn_weights=average_attn_weights, is_causal=is_causal)
+        # (S, B, E) views of batch-first activations (transformer.encoder runs the stack
+        # batch-first): run on the (B, S, E) rows as they lie, no transposed copy.  (With one
+        # sample both layouts are the same rows; batch-first keeps the caller's strides.)
+        bf = query.transpose(0, 1).is_contiguous() and key.transpose(0, 1).is_contiguous() and \
+            not (query.shape[1] > 1 and query.is_contiguous() and key.is_contiguous())
+        if bf:
+            query, key = query.transpose(0, 1), key.transpose(0, 1)
+        H, W, bias = self.num_heads, self.in_proj_weight, self.in_proj_bias
+        causal = attn_mask is not None  # _core_fusable: a mask here is the declared causal one
+        if _same(query, key):
+            q, kv = nn_ops.linear(query, W, bias), None
+        else:
+            q, kv, _, _ = nn_ops.in_proj_qkv(query, key, W, bias, self.embed_dim)
+        if need_weights:
+            o, w = attention(q, kv, H, causal, key_padding_mask, batch_first=bf, need_weights=True,
+                             average=average_attn_weights)
+        else:
+            o, w = attention(q, kv, H, causal, key_padding_mask, batch_first=bf), None
+        out = nn_ops.linear(o, self.out_proj.weight, self.out_proj.bias)
+        return (out.transpose(0, 1) if bf else out), w
+
+
+def retarget(stack):
+    """Make every nn.MultiheadAttention of a transformer stack a MultiheadAttention, in place
+    (the class of the module torch built is switched; no module is constructed, so parameters,
+    state-dict keys and the RNG stream of the model's constructor are untouched)."""
+    for mod in stack.modules():
+        if type(mod) is nn.MultiheadAttention:
+            mod.__class__ = MultiheadAttention
+    return stack

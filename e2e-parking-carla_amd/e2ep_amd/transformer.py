@@ -7,8 +7,9 @@ here with the same math and the same submodules, except that each "x + dropout(s
 -> LayerNorm" runs as one e2ep kernel (nn_ops.add_drop_layer_norm) instead of PyTorch's
 dropout + add + layer_norm (+ its slow gamma/beta backward).  The attention core (QK^T, mask,
 softmax, dropout, PV and their backward) runs as e2ep kernels through attention.mha, which
-keeps the modules' own in/out projections (hipBLASLt GEMMs) and falls back to the module when
-a hook is installed (the agent's attention capture)."""
+keeps the modules' own in/out projections (e2ep_gemm launches) and calls the module when a
+hook is installed (the agent's attention capture); the model's modules are
+attention.MultiheadAttention, whose own forward is the same fused path plus the weights."""
 
 import torch
 import torch.nn.functional as F

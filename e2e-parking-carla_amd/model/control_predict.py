@@ -6,7 +6,7 @@ output).  `forward` is the teacher-forced training path, `predict` one autoregre
 import torch
 from torch import nn
 
-from e2ep_amd import _lib, nn_ops, transformer
+from e2ep_amd import _lib, attention, nn_ops, transformer
 
 
 class ControlPredict(nn.Module):
@@ -21,6 +21,7 @@ class ControlPredict(nn.Module):
         layer = nn.TransformerDecoderLayer(d_model=cfg.tf_de_dim, nhead=cfg.tf_de_heads,
                                            dropout=0.0 if det else 0.1)
         self.tf_decoder = nn.TransformerDecoder(layer, num_layers=cfg.tf_de_layers)
+        attention.retarget(self.tf_decoder)  # self_attn / multihead_attn: see FeatureFusion
         self.output = nn.Linear(cfg.tf_de_dim, cfg.token_nums)
         for name, p in self.named_parameters():
             if "pos_embed" not in name and p.dim() > 1:

@@ -3,11 +3,13 @@
 Mirrors reference model/feature_fusion.py:8-51 (keys: tf_encoder.layers.i.*, pos_embed,
 motion_encoder.{0,2,4}).  The encoder layers stay `nn.TransformerEncoderLayer` modules so
 the closed-loop agent's attention hook (agent/parking_agent.py:71-80,266-268) keeps working;
-their arithmetic runs through e2ep_amd.transformer."""
+their arithmetic runs through e2ep_amd.transformer, and their attention modules are
+e2ep_amd.attention.MultiheadAttention (the class of the modules torch built is switched), so
+the hooked call returns its attention weights from the e2ep kernels."""
 import torch
 from torch import nn
 
-from e2ep_amd import nn_ops, transformer
+from e2ep_amd import attention, nn_ops, transformer
 
 
 class FeatureFusion(nn.Module):
@@ -19,6 +21,9 @@ class FeatureFusion(nn.Module):
                                            dropout=0.0 if det else 0.1)
         self.tf_encoder = nn.TransformerEncoder(layer, num_layers=cfg.tf_en_layers,
                                                 enable_nested_tensor=False)
+        # the layers' self_attn become attention.MultiheadAttention (class switch, nothing is
+        # constructed): a hooked / patched module then returns its weights from the e2ep kernels
+        attention.retarget(self.tf_encoder)
         self.pos_embed = nn.Parameter(torch.randn(1, cfg.tf_en_bev_length, cfg.tf_en_dim) * .02)
         self.pos_drop = nn.Dropout(0.0 if det else cfg.tf_en_dropout)
         u = cfg.tf_en_bev_length // 4

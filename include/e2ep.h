@@ -465,6 +465,17 @@ int e2ep_attn_fwd(const float *q, const float *k, const float *v, int B, int H, 
                   int dh, int q_ss, int q_sb, int kv_ss, int kv_sb, int o_ss, int o_sb,
                   float scale, int causal, const uint8_t *key_pad, float p, const int32_t *seed,
                   float *o, float *lse, void *stream);
+/* Attention probabilities of e2ep_attn_fwd's softmax (before dropout), recomputed from Q, K and
+ * the forward's lse.  average = 0: w is [B][H][Sq][Sk]; average = 1: w is [B][Sq][Sk], the mean
+ * over heads (fixed order).  Masked entries and fully masked rows are 0.
+ * q, k, the strides, scale, causal and key_pad are those given to the e2ep_attn_fwd call that
+ * wrote lse (P_ij = exp2(scale log2(e) q_i . k_j - lse_i), the matrix that forward normalised;
+ * what torch.nn.MultiheadAttention returns with need_weights=True, agent/parking_agent.py:71-91).
+ * w is fp32, contiguous.  A separate launch: a forward without weights runs nothing extra.  The
+ * same shape limits and error codes as e2ep_attn_fwd; the same kernel family (e2ep_tune key 21). */
+int e2ep_attn_weights(const float *q, const float *k, const float *lse, int B, int H, int Sq,
+                      int Sk, int dh, int q_ss, int q_sb, int kv_ss, int kv_sb, float scale,
+                      int causal, const uint8_t *key_pad, int average, float *w, void *stream);
 size_t e2ep_attn_bwd_workspace(int B, int H, int Sq);
 int e2ep_attn_bwd(const float *q, const float *k, const float *v, const float *o, const float *dout,
                   const float *lse, int B, int H, int Sq, int Sk, int dh, int q_ss, int q_sb,
