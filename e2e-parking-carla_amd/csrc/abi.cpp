@@ -24,8 +24,9 @@ void set_error(const char *fmt, ...) {
 // B = 8 eval-mode gradient-norm parity (test_model_b8_gpu) past its bound (1.36e-4 vs fp64 on
 // one camera-encoder BN weight), and the fp32 data gradient (mask 8) alone is neutral, so fp32
 // stays on the implicit GEMMs; the direct weight gradient (mask 4) is neutral in C3 and slower
-// than k_conv_wgrad2 in fp32 (profiles/r06/stem_direct_ab.txt).
-int g_tune[TUNE_N] = {8192, 4096, 512, 512, 768, 1024, 512, 1, 1, 2, 1, 2, 2, 1, 2, 1, 1, 1, 1, 1, 1, 2, 1024, 2, 2048, 2, 1, 1, 2, 1, 2, 1, 1, 1, 1, 4};
+// than k_conv_wgrad2 in fp32 (profiles/r06/stem_direct_ab.txt).  Key 36 = 2: the 16x16 MBConv
+// middle in one launch per direction (mbconv_mid.hip; profiles/mbconv_mid/).
+int g_tune[TUNE_N] = {8192, 4096, 512, 512, 768, 1024, 512, 1, 1, 2, 1, 2, 2, 1, 2, 1, 1, 1, 1, 1, 1, 2, 1024, 2, 2048, 2, 1, 1, 2, 1, 2, 1, 1, 1, 1, 4, 2};
 }  // namespace e2ep
 
 extern "C" {

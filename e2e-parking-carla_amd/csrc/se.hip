@@ -436,11 +436,11 @@ __global__ void __launch_bounds__(256) k_se_dx(const float *__restrict__ dy,
 
 using namespace e2ep;
 
-extern "C" {
-
-int e2ep_se_fwd(const void *x, const float *x_scale, const float *x_shift, const float *w1,
-                const float *b1, const float *w2, const float *b2, int N, int C, int HW, int sq,
-                float *pooled, float *hpre, float *a, void *y, void *stream, int io) {
+// squeeze = false (e2ep_se_fwd_pooled): pooled is the caller's, the squeeze pass is not run
+static int se_fwd_impl(const void *x, const float *x_scale, const float *x_shift, const float *w1,
+                       const float *b1, const float *w2, const float *b2, int N, int C, int HW, int sq,
+                       float *pooled, float *hpre, float *a, void *y, void *stream, int io,
+                       bool squeeze) {
   E2EP_REQUIRE(io == 0 || ((io == E2EP_IO_X_BF16 || io == (E2EP_IO_X_BF16 | E2EP_IO_DX_BF16)) &&
                            HW % 4 == 0),
                E2EP_EINVAL, "e2ep_se_fwd: storage mask %d not supported (0, X or X|DX bf16, "
@@ -455,7 +455,9 @@ int e2ep_se_fwd(const void *x, const float *x_scale, const float *x_shift, const
   const int vec = (HW & 3) == 0;
   const long long nvec = (long long)planes * HW / (vec ? 4 : 1);
   E2EP_REQUIRE(nvec < (1LL << 29), E2EP_ERANGE, "e2ep_se_fwd: %lld vectors >= 2^29", nvec);
-  if (io)
+  if (!squeeze)
+    ;
+  else if (io)
     hipLaunchKernelGGL(k_se_squeeze<bf16_t>, dim3(cdiv(planes, 4)), dim3(256), 0, s,
                        static_cast<const bf16_t *>(x), tf, planes, HW, pooled);
   else
@@ -489,6 +491,24 @@ int e2ep_se_fwd(const void *x, const float *x_scale, const float *x_shift, const
     hipLaunchKernelGGL((k_se_excite<float, float>), dim3(cdiv(nvec, 256)), dim3(256), 0, s,
                        static_cast<const float *>(x), tf, a, HW, nvec, vec, static_cast<float *>(y));
   return launch_status("e2ep_se_fwd");
+}
+
+extern "C" {
+
+int e2ep_se_fwd(const void *x, const float *x_scale, const float *x_shift, const float *w1,
+                const float *b1, const float *w2, const float *b2, int N, int C, int HW, int sq,
+                float *pooled, float *hpre, float *a, void *y, void *stream, int io) {
+  return se_fwd_impl(x, x_scale, x_shift, w1, b1, w2, b2, N, C, HW, sq, pooled, hpre, a, y, stream,
+                     io, true);
+}
+
+int e2ep_se_fwd_pooled(const void *x, const float *x_scale, const float *x_shift, const float *w1,
+                       const float *b1, const float *w2, const float *b2, int N, int C, int HW,
+                       int sq, const float *pooled, float *hpre, float *a, void *y, void *stream,
+                       int io) {
+  E2EP_REQUIRE(pooled, E2EP_EINVAL, "e2ep_se_fwd_pooled: pooled is required");
+  return se_fwd_impl(x, x_scale, x_shift, w1, b1, w2, b2, N, C, HW, sq,
+                     const_cast<float *>(pooled), hpre, a, y, stream, io, false);
 }
 
 static int se_bwd_impl(const void *x, int io, const float *x_scale, const float *x_shift,

@@ -105,6 +105,10 @@ SIGNATURES = {
     "e2ep_relu_dropout_fwd": (_i, [_p, _i64, _f, _p, _p, _p]),
     "e2ep_relu_dropout_bwd": (_i, [_p, _p, _i64, _f, _p, _p, _p]),
     "e2ep_se_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i]),
+    "e2ep_se_fwd_pooled": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i]),
+    "e2ep_mbconv_mid_ok": (_i, [_p]),
+    "e2ep_mbconv_mid_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p]),
+    "e2ep_mbconv_mid_bwd": (_i, [_p] * 20),
     "e2ep_se_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i]),
     "e2ep_se_bwd_bn": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i]),
     "e2ep_bn_bwd_planes": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i]),

@@ -845,6 +845,117 @@ def bn_swish_squeeze_excite(x, bn, w1, b1, w2, b2):
                             *(pp or (None, 0)), None if train else _eval_bn_stats(bn))
 
 
+# ------------------------------------------------------------------------------------------
+# MBConv middle on 16x16 maps: _bn0 -> swish -> depthwise -> _bn1 -> swish -> SE, the chain up
+# to the SE squeeze in one launch per direction (csrc/mbconv_mid.hip, e2ep_tune key 36)
+# ------------------------------------------------------------------------------------------
+def _bn_trains(bn):
+    return bn.training or not bn.track_running_stats
+
+
+def _mid_dims(N, C, H, W, w, stride, pad):
+    K = w.shape[-1]
+    l, r, t, b = pad
+    P = (H + t + b - K) // stride + 1
+    Q = (W + l + r - K) // stride + 1
+    return (N, C, H, W, K, P, Q, stride, t, l)
+
+
+def mbconv_mid_ok(shape, dtype, bn0, bn1, w, stride, pad):
+    """True when bn_act_depthwise_conv2d + bn_swish_squeeze_excite on an input of `shape` run
+    as the fused op (mbconv_mid): training statistics for both BatchNorms, fp32 storage, and a
+    shape e2ep_mbconv_mid_ok takes."""
+    if dtype != torch.float32 or not (_bn_trains(bn0) and _bn_trains(bn1)) or _store_bf16(True):
+        return False
+    return _lib.load().e2ep_mbconv_mid_ok(_lib.dims(_mid_dims(*shape, w, stride, pad))) == 1
+
+
+class _MBConvMid(torch.autograd.Function):
+    """squeeze_excite(swish(bn1(depthwise(swish(bn0(x)))))) of an MBConv block on 16x16 maps:
+    _BnActDwConv followed by _BnSwishSE with the launches up to the SE squeeze fused
+    (e2ep_mbconv_mid_fwd), and in the backward everything after the SE's own gradient kernels
+    (e2ep_mbconv_mid_bwd).  Same results bit for bit (the depthwise weight gradient where the
+    separate kernel takes one split per channel, C >= 512; else the same sums in another order)."""
+
+    @staticmethod
+    def forward(ctx, x, g0, b0, rm0, rv0, mom0, eps0, w, dims, g1, b1, rm1, rv1, mom1, eps1,
+                w1, sb1, w2, sb2):
+        x = x.contiguous()
+        w = w.contiguous()
+        N, C = dims[:2]
+        sq = w1.shape[0]
+        f32 = dict(dtype=torch.float32, device=x.device)
+        st0, st1 = torch.empty(4, C, **f32), torch.empty(4, C, **f32)  # mean, invstd, scale, shift
+        y1, pooled = torch.empty_like(x), torch.empty(N, C, **f32)
+        s = _lib.stream()
+        with timing.region(timing.name("mbconv_mid_fwd", x.shape, "_MBConvMid")):
+            _lib.call("e2ep_mbconv_mid_fwd", _lib.ptr(x), _lib.ptr(w), _lib.dims(dims), _lib.ptr(g0),
+                      _lib.ptr(b0), _lib.ptr(rm0), _lib.ptr(rv0), float(mom0), float(eps0),
+                      _lib.ptr(st0), _lib.ptr(g1), _lib.ptr(b1), _lib.ptr(rm1), _lib.ptr(rv1),
+                      float(mom1), float(eps1), _lib.ptr(st1), _lib.ptr(y1), _lib.ptr(pooled), s)
+        hpre, a, y = torch.empty(N, sq, **f32), torch.empty(N, C, **f32), torch.empty_like(x)
+        w1c, w2c = w1.reshape(sq, C).contiguous(), w2.reshape(C, sq).contiguous()
+        with timing.region(timing.name("se_fwd", x.shape, "_MBConvMid")):
+            _lib.call("e2ep_se_fwd_pooled", _lib.ptr(y1), _lib.ptr(st1[2]), _lib.ptr(st1[3]),
+                      _lib.ptr(w1c), _lib.ptr(sb1), _lib.ptr(w2c), _lib.ptr(sb2), N, C, 256, sq,
+                      _lib.ptr(pooled), _lib.ptr(hpre), _lib.ptr(a), _lib.ptr(y), s, 0)
+        ctx.save_for_backward(x, y1, w, g0, b0, st0, g1, b1, st1, w1c, w2c, pooled, hpre, a)
+        ctx.dims = dims
+        ctx.shapes = (w1.shape, w2.shape, sb1 is not None, sb2 is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y1, w, g0, b0, st0, g1, b1, st1, w1c, w2c, pooled, hpre, a = ctx.saved_tensors
+        w1s, w2s, hb1, hb2 = ctx.shapes
+        N, C = ctx.dims[:2]
+        sq = w1c.shape[0]
+        nig = ctx.needs_input_grad
+        f32 = dict(dtype=torch.float32, device=x.device)
+        dy = dy.contiguous()
+        s = _lib.stream()
+        dw1 = torch.empty(w1s, **f32) if nig[15] else None
+        dsb1 = torch.empty(sq, **f32) if (hb1 and nig[16]) else None
+        dw2 = torch.empty(w2s, **f32) if nig[17] else None
+        dsb2 = torch.empty(C, **f32) if (hb2 and nig[18]) else None
+        dpooled = torch.empty(N, C, **f32)
+        ws = torch.empty(2 * N * C + 17 * N * sq, **f32)
+        with timing.region(timing.name("se_bwd", x.shape, "_MBConvMid")):
+            _lib.call("e2ep_se_bwd", _lib.ptr(y1), _lib.ptr(st1[2]), _lib.ptr(st1[3]), _lib.ptr(dy),
+                      _lib.ptr(w1c), _lib.ptr(w2c), _lib.ptr(pooled), _lib.ptr(hpre), _lib.ptr(a),
+                      N, C, 256, sq, None, _lib.ptr(dpooled), _lib.ptr(dw1), _lib.ptr(dsb1),
+                      _lib.ptr(dw2), _lib.ptr(dsb2), _lib.ptr(ws), s, 0)
+        dx, dw = torch.empty_like(x), torch.empty_like(w)
+        dg0 = torch.empty_like(g0) if (g0 is not None and nig[1]) else None
+        db0 = torch.empty_like(b0) if (b0 is not None and nig[2]) else None
+        dg1 = torch.empty_like(g1) if (g1 is not None and nig[9]) else None
+        db1 = torch.empty_like(b1) if (b1 is not None and nig[10]) else None
+        with timing.region(timing.name("mbconv_mid_bwd", x.shape, "_MBConvMid")):
+            _lib.call("e2ep_mbconv_mid_bwd", _lib.ptr(dy), _lib.ptr(a), _lib.ptr(dpooled),
+                      _lib.ptr(y1), _lib.ptr(x), _lib.ptr(w), _lib.dims(ctx.dims), _lib.ptr(st1),
+                      _lib.ptr(g1), _lib.ptr(b1), _lib.ptr(st0), _lib.ptr(g0), _lib.ptr(b0),
+                      _lib.ptr(dx), _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dg0), _lib.ptr(db0),
+                      _lib.ptr(dw), s)
+        return (dx if nig[0] else None, dg0, db0, None, None, None, None, dw if nig[7] else None,
+                None, dg1, db1, None, None, None, None, dw1, dsb1, dw2, dsb2)
+
+
+def mbconv_mid(x, bn0, w, stride, pad, bn1, w1, b1, w2, b2):
+    """bn_swish_squeeze_excite(bn_act_depthwise_conv2d(x, bn0, 'swish', w, stride, pad), bn1,
+    w1, b1, w2, b2) as one op; the caller has checked mbconv_mid_ok."""
+    _dev(x)
+    _bn_train_and_count(bn0)
+    _bn_train_and_count(bn1)
+
+    def args(bn):
+        rs = bn.track_running_stats
+        return (bn.weight, bn.bias, bn.running_mean if rs else None, bn.running_var if rs else None,
+                bn.momentum if bn.momentum is not None else 0.1, bn.eps)
+
+    dims = _mid_dims(*x.shape, w, stride, pad)
+    return _MBConvMid.apply(x, *args(bn0), w, dims, *args(bn1), w1, b1, w2, b2)
+
+
 def squeeze_excite(x, w1, b1, w2, b2):
     """x * sigmoid(w2 swish(w1 mean_hw(x) + b1) + b2): efficientnet-pytorch MBConv SE with the
     two 1x1 convs (w1 [sq,C,1,1], w2 [C,sq,1,1]) on the pooled 1x1 map."""

@@ -76,6 +76,24 @@ def bn_swish_squeeze_excite(x, bn, reduce, expand):
                                           expand.bias)
 
 
+def mbconv_mid_ok(shape, dtype, bn0, conv, bn1):
+    """True when mbconv_mid takes an expand-conv output of `shape` / `dtype` for these layers
+    (16x16 maps, stride 1, training statistics, fp32 storage: nn_ops.mbconv_mid_ok); the caller
+    then asks the expand conv for no BatchNorm partials."""
+    s = _pair(conv.stride)
+    return s[0] == s[1] and nn_ops.mbconv_mid_ok(shape, dtype, bn0, bn1, conv.weight, s[0],
+                                                 _pad4(conv.same))
+
+
+def mbconv_mid(x, bn0, conv, bn1, reduce, expand):
+    """bn_swish_squeeze_excite(bn_act_depthwise(x, bn0, 'swish', conv), bn1, reduce, expand)
+    with everything up to the SE squeeze in one launch (one more in the backward): one
+    workgroup per channel holds the channel of a 16x16 stage in registers."""
+    assert conv.groups == x.shape[1] and conv.bias is None
+    return nn_ops.mbconv_mid(x, bn0, conv.weight, _pair(conv.stride)[0], _pad4(conv.same), bn1,
+                             reduce.weight, reduce.bias, expand.weight, expand.bias)
+
+
 def upsample2x(x):
     return nn_ops.resize(x, scale_factor=2)
 

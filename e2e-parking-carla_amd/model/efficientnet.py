@@ -81,18 +81,29 @@ class MBConv(nn.Module):
             y = ops.bn_act_depthwise(e, self._bn0, "swish", self._depthwise_conv, st)
             y = ops.bn_swish_squeeze_excite(y, self._bn1, self._se_reduce, self._se_expand)
             return ops.bn_act(self._project_conv(y, st), self._bn2, None), xa
+        mid = False
         if self.expand != 1:  # _bn0 + swish applied inside the depthwise conv's input load
+            # 16x16 training maps: _bn0 .. SE squeeze in one launch, which takes its own
+            # statistics (no BN partials from the expand conv's epilogue)
+            mid = x.is_cuda and ops.mbconv_mid_ok(
+                (x.shape[0], self._bn0.num_features) + tuple(x.shape[2:]), x.dtype, self._bn0,
+                self._depthwise_conv, self._bn1)
             if self.skip and x.is_cuda:
-                e, x = self._expand_conv.forward_skip(x, st)
+                e, x = self._expand_conv.forward_skip(x, st and not mid)
             else:
-                e = self._expand_conv(x, st)
-            y = ops.bn_act_depthwise(e, self._bn0, "swish", self._depthwise_conv, st)
+                e = self._expand_conv(x, st and not mid)
+            if mid:
+                y = ops.mbconv_mid(e, self._bn0, self._depthwise_conv, self._bn1, self._se_reduce,
+                                   self._se_expand)
+            else:
+                y = ops.bn_act_depthwise(e, self._bn0, "swish", self._depthwise_conv, st)
         elif self.skip and x.is_cuda:  # x feeds the depthwise conv and the skip (nn_ops.fork2)
             xd, x = nn_ops.fork2(x)
             y = self._depthwise_conv(xd, st)
         else:
             y = self._depthwise_conv(x, st)
-        y = ops.bn_swish_squeeze_excite(y, self._bn1, self._se_reduce, self._se_expand)
+        if not mid:
+            y = ops.bn_swish_squeeze_excite(y, self._bn1, self._se_reduce, self._se_expand)
         if not self.skip:
             return ops.bn_act(self._project_conv(y, st), self._bn2, None)
         if drop_connect_rate and self.training:

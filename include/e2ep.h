@@ -416,6 +416,45 @@ int e2ep_se_bwd_bn(const void *x, const float *x_scale, const float *x_shift,
                    int sq, float *dpooled_out, float *dw1, float *db1, float *dw2, float *db2,
                    double *plane_sums, float *workspace, void *stream,
                    int io /* 0, X or X|DY bf16 */);
+/* e2ep_se_fwd from a pooled [N,C] the caller already holds (e2ep_mbconv_mid_fwd writes it):
+ * the squeeze pass over x is not run; hpre, a and y as e2ep_se_fwd computes them. */
+int e2ep_se_fwd_pooled(const void *x, const float *x_scale, const float *x_shift, const float *w1,
+                       const float *b1, const float *w2, const float *b2, int N, int C, int HW,
+                       int sq, const float *pooled, float *hpre, float *a, void *y, void *stream,
+                       int io /* as e2ep_se_fwd */);
+
+/* ---------------------------------------------------------------------------------------
+ * The middle of an MBConv block on 16x16 maps, one launch per direction (mbconv_mid.hip):
+ *   y1 = depthwise(swish(bn0(y0)));  pooled = mean_hw swish(bn1(y1))
+ * with training statistics for both BatchNorms — what e2ep_bn_stats, e2ep_dwconv_fwd,
+ * e2ep_bn_stats and e2ep_se_fwd's squeeze compute in four launches, and in the backward
+ * e2ep_bn_bwd (_bn1, squeeze-excitation gate), e2ep_dwconv_bwd and e2ep_bn_bwd (_bn0) in
+ * three.  One workgroup per channel holds the channel in registers.  Every output is bitwise
+ * that of the separate launches; dw too where e2ep_dwconv_bwd sums one split per channel
+ * (C >= 512), else the same terms in another fixed order.
+ * dims[10] as the depthwise entry points.  e2ep_mbconv_mid_ok: 1 when the shape is taken —
+ * H = W = P = Q = 16, stride 1, K 3 | 5 with SAME padding, N * 256 <= 8192, the BatchNorms on
+ * their single-launch kernels, e2ep_tune key 36 = 2 — else 0, and the two entry points then
+ * return E2EP_EINVAL.  fp32 storage only.
+ * stats0 / stats1 [4][C]: mean, invstd, scale, shift of _bn0 / _bn1 (forward outputs, backward
+ * inputs); gamma / beta nullable (1 / 0); running_mean / running_var both or neither.
+ * Backward: gy is the gradient at the squeeze-excitation output, gate_logit / gate_dpooled
+ * [N,C] as e2ep_bn_bwd takes them (a and dpooled_out of e2ep_se_bwd); dx [N,C,16,16] the
+ * gradient at y0, dw [C,K,K]; dgamma / dbeta nullable.
+ * ------------------------------------------------------------------------------------- */
+int e2ep_mbconv_mid_ok(const int *dims);
+int e2ep_mbconv_mid_fwd(const float *y0, const float *w, const int *dims, const float *gamma0,
+                        const float *beta0, float *running_mean0, float *running_var0,
+                        float momentum0, float eps0, float *stats0, const float *gamma1,
+                        const float *beta1, float *running_mean1, float *running_var1,
+                        float momentum1, float eps1, float *stats1, float *y1, float *pooled,
+                        void *stream);
+int e2ep_mbconv_mid_bwd(const float *gy, const float *gate_logit, const float *gate_dpooled,
+                        const float *y1, const float *y0, const float *w, const int *dims,
+                        const float *stats1, const float *gamma1, const float *beta1,
+                        const float *stats0, const float *gamma0, const float *beta0, float *dx,
+                        float *dgamma1, float *dbeta1, float *dgamma0, float *dbeta0, float *dw,
+                        void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Residual add + dropout + LayerNorm of the post-norm transformer layers (torch
