@@ -160,7 +160,16 @@ __global__ void __launch_bounds__(256) k_embed_tokens_bwd(
 // Autoregressive decode step (reference model/control_predict.py:70-75): softmax of one
 // logits row, argmax of the probabilities (torch.argmax: the first index of the largest
 // value), the token written into column `pos` of the persistent sequence.  Block per row; the
-// max and the sum reduce in a fixed order (deterministic).
+// max and the sum reduce in a fixed order (deterministic).  A row holding a NaN or a +inf, or
+// only -inf, has NaN probabilities; torch.argmax ranks NaN above every number, so the order
+// below does too (the first NaN wins) and the token stays inside [0, V).
+__device__ __forceinline__ bool argmax_beats(float a, int ai, float b, int bi) {
+  const bool an = a != a, bn = b != b;
+  if (an != bn) return an;
+  if (an) return ai < bi;
+  return a > b || (a == b && ai < bi);
+}
+
 __global__ void __launch_bounds__(256) k_token_argmax_append(const float *__restrict__ logits,
                                                              long long rstride, int V,
                                                              int64_t *__restrict__ seq,
@@ -188,7 +197,7 @@ __global__ void __launch_bounds__(256) k_token_argmax_append(const float *__rest
   int bi = 0x7fffffff;
   for (int v = tid; v < V; v += 256) {
     const float p = expf(row[v] - m) / s;
-    if (p > best) {  // v ascends per thread: the first index of a tie is kept
+    if (p > best || (p != p && best == best)) {  // v ascends: the first of a tie (or NaN) is kept
       best = p;
       bi = v;
     }
@@ -197,7 +206,7 @@ __global__ void __launch_bounds__(256) k_token_argmax_append(const float *__rest
   for (int o = 32; o > 0; o >>= 1) {
     const float ob = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) {
+    if (argmax_beats(ob, oi, best, bi)) {
       best = ob;
       bi = oi;
     }
@@ -209,7 +218,7 @@ __global__ void __launch_bounds__(256) k_token_argmax_append(const float *__rest
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < 4; ++w)
-      if (sf[w] > best || (sf[w] == best && si[w] < bi)) {
+      if (argmax_beats(sf[w], si[w], best, bi)) {
         best = sf[w];
         bi = si[w];
       }

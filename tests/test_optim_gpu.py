@@ -90,3 +90,82 @@ def test_flat_adam_gathered_grads_equal_table_grads():
         ob.step(flat, 0.5)
     for p, q in zip(a, b):
         assert torch.equal(p.detach(), q.detach())
+
+
+def test_flat_adam_unaligned_gradient_equals_aligned_bitwise():
+    """k_adam's scalar path (csrc/adam.hip:53, 83-85): the gradient of the 4097-element tensor
+    (a length that is no multiple of 4, two chunks) is a view one float into a larger buffer, so
+    it is not 16-byte aligned.  Result: bitwise the aligned run's, and torch.optim.Adam's to 1e-6."""
+    from e2ep_amd.optim import FlatAdam
+    ref, a, b = _params(3), _params(3), _params(3)
+    topt = torch.optim.Adam(ref, lr=1e-3, weight_decay=1e-4, foreach=False)
+    oa, ob = FlatAdam(a, lr=1e-3, weight_decay=1e-4), FlatAdam(b, lr=1e-3, weight_decay=1e-4)
+    for k in range(3):
+        gs = _grads(k)
+        for i, (r, p, q, g) in enumerate(zip(ref, a, b, gs)):
+            r.grad, p.grad = g.clone(), g.clone()
+            if i == 2:
+                buf = torch.zeros(g.numel() + 8, device=DEV)
+                q.grad = buf[1:1 + g.numel()].copy_(g)
+                assert q.grad.data_ptr() % 16 == 4 and p.grad.data_ptr() % 16 == 0
+            else:
+                q.grad = g.clone()
+        topt.step()
+        oa.step()
+        ob.step()
+    for r, p, q in zip(ref, a, b):
+        assert torch.equal(p.detach(), q.detach())
+        assert rel_l2(q.detach(), r.detach()) < 1e-6
+    assert torch.equal(oa.exp_avg, ob.exp_avg) and torch.equal(oa.exp_avg_sq, ob.exp_avg_sq)
+
+
+def test_flat_adam_zero_and_tiny_gradients():
+    """The eps denominator: an all-zero gradient on the first step (0 / eps: nothing moves, as
+    torch), then a gradient of 1e-20 (sqrt(v) ~ 3e-22 << eps), then an ordinary one.  Parameters of
+    scale 1e-12 make the 1e-20 step visible.  Parameters and exp_avg to 1e-6; exp_avg_sq after
+    the 1e-20 step is an fp32 subnormal (1e-43), compared to one subnormal quantum (1.4e-45)."""
+    from e2ep_amd.optim import FlatAdam
+    shapes = [(5,), (4097,), (3, 7)]
+    g = torch.Generator().manual_seed(9)
+    init = [torch.randn(s, generator=g) * sc for s, sc in zip(shapes, (1.0, 1e-12, 1.0))]
+    ref = [t.clone().to(DEV).requires_grad_() for t in init]
+    mine = [t.clone().to(DEV).requires_grad_() for t in init]
+    topt = torch.optim.Adam(ref, lr=1e-3, foreach=False)
+    fopt = FlatAdam(mine, lr=1e-3)
+    for k, fill in enumerate((0.0, 1e-20, None)):
+        for p, q in zip(ref, mine):
+            gr = torch.randn(p.shape, generator=g).to(DEV) if fill is None else torch.full_like(p, fill)
+            p.grad, q.grad = gr.clone(), gr.clone()
+        topt.step()
+        fopt.step()
+        sd, tsd = fopt.state_dict()["state"], topt.state_dict()["state"]
+        for i, (p, q) in enumerate(zip(ref, mine)):
+            if k == 0:
+                assert torch.equal(q.detach().cpu(), init[i])
+                assert torch.equal(p.detach().cpu(), init[i])
+            assert rel_l2(q.detach(), p.detach()) < 1e-6
+            assert rel_l2(sd[i]["exp_avg"], tsd[i]["exp_avg"]) < 1e-6
+            assert torch.allclose(sd[i]["exp_avg_sq"], tsd[i]["exp_avg_sq"], rtol=1e-6, atol=1.5e-45)
+        if k == 1:
+            assert not torch.equal(mine[1].detach().cpu(), init[1])  # the 1e-20 step moved it
+
+
+def test_flat_adam_follows_learning_rate_changes():
+    """The learning rate changed between eager steps through param_groups (what an LR scheduler
+    writes): the kernel reads the new value from its device scalar (sync_lr)."""
+    from e2ep_amd.optim import FlatAdam
+    ref, mine = _params(4), _params(4)
+    topt = torch.optim.Adam(ref, lr=1e-3, weight_decay=1e-4, foreach=False)
+    fopt = FlatAdam(mine, lr=1e-3, weight_decay=1e-4)
+    for k, lr in enumerate((1e-3, 7e-3, 7e-3, 2.5e-5, 0.0)):
+        topt.param_groups[0]["lr"] = lr
+        fopt.param_groups[0]["lr"] = lr
+        for p, q, g in zip(ref, mine, _grads(k)):
+            p.grad, q.grad = g.clone(), g.clone()
+        before = [q.detach().clone() for q in mine]
+        topt.step()
+        fopt.step()
+        for p, q, b in zip(ref, mine, before):
+            assert rel_l2(q.detach(), p.detach()) < 1e-6
+            if lr == 0.0:
+                assert torch.equal(q.detach(), b)
