@@ -126,6 +126,11 @@ SIGNATURES = {
     "e2ep_capture_unjoined": (_i, [_p, _p, ctypes.POINTER(_i)]),
     "e2ep_tokens_init": (_i, [_p, _i, _i, _i, _p, _i, _i64, _p]),
     "e2ep_token_argmax_append": (_i, [_p, _i64, _i, _i, _p, _i, _i, _p]),
+    "e2ep_dec_self_attn": (_i, [_p, _i, _p, _p, _f, _p, _i, _p, _p, _p, _i, _i64, _p, _p, _p, _p,
+                                _i, _i, _i, _i, _i, _p]),
+    "e2ep_dec_cross_attn": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _i, _p, _i, _i, _i, _i, _p]),
+    "e2ep_dec_row_gemv": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _i, _p, _p, _f, _p, _i, _i, _i, _i,
+                               _i, _p]),
     "e2ep_dwconv_bf16_ok": (_i, [_p]),
     "e2ep_control_ce_workspace": (_sz, [_i]),
     "e2ep_control_ce_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

@@ -6,7 +6,7 @@ output).  `forward` is the teacher-forced training path, `predict` one autoregre
 import torch
 from torch import nn
 
-from e2ep_amd import _lib, attention, nn_ops, transformer
+from e2ep_amd import _lib, ar_decode, attention, nn_ops, transformer
 
 
 class ControlPredict(nn.Module):
@@ -75,13 +75,18 @@ class ControlPredict(nn.Module):
         persistent sequence buffer: the PAD padding, softmax, argmax and torch.cat of every
         step are two e2ep launches in all (e2ep_tokens_init once, e2ep_token_argmax_append per
         step), no host sync, HIP-graph capturable.  Returns the (B, L + steps) tokens (a view
-        of the buffer)."""
+        of the buffer).  Where ar_decode.eligible (eval, no autograd, fp32 HIP tensors, B <= 16,
+        no hook on the decoder ...) each step decodes only its new position against per-layer
+        K/V caches instead of re-running the decoder over all T positions: the same tokens."""
         B, L = toks.shape
         T = self.cfg.tf_de_tgt_dim - 1
         if not (toks.is_cuda and toks.dtype == torch.long and L + steps <= T and steps > 0):
             for _ in range(steps):  # the reference's own loop (it raises where L + steps > T)
                 toks = torch.cat([toks, self.predict(encoder_out, toks)], dim=1)
             return toks
+        if ar_decode.eligible(self, encoder_out, toks):
+            # KV-cached: one new row per step instead of the full pass (e2ep_amd/ar_decode.py)
+            return ar_decode.decode_tokens(self, encoder_out, toks, steps)
         seq = torch.empty((B, T), dtype=torch.long, device=toks.device)
         s = _lib.stream()
         _lib.call("e2ep_tokens_init", _lib.ptr(toks), toks.stride(0), B, L, _lib.ptr(seq), T,

@@ -667,6 +667,45 @@ int e2ep_embed_tokens_bwd(const float *dout, const int64_t *tok, int tok_stride,
                           void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Incremental (KV-cached) decoding of the control-token decoder (ar_decode.hip; added within
+ * ABI 4): one new position t per sample and step instead of the full (B, T) pass of reference
+ * model/control_predict.py:60-75.  Post-norm ReLU layers; six launches per layer and step
+ * (self attention, out-projection, cross attention, out-projection, FFN1, FFN2).  The rows
+ * kept in memory are the pre-norm sums: an entry point that takes (gamma, beta, eps) with a
+ * row applies torch's LayerNorm (biased variance) as it loads the row; gamma null = the row as
+ * it is, beta null = 0.  fp32, fixed-order reductions, no atomics: bitwise repeatable.
+ * Limits (E2EP_ERANGE beyond, nothing launched): B <= 16, T <= 32, Sk <= 256, head dim
+ * E / H <= 64, row length E / K <= 4088.  Rows use 8-byte loads when E (K) is even and the
+ * weight 8-byte aligned, else dword loads.
+ *
+ * e2ep_dec_self_attn: grid (H, B).  Input row of sample b: LN(x[b * ldx ..]) or, with x null
+ *   (the first layer), table[clamp(seq[b][t], 0, V - 1)] + pos[t], which is also written to
+ *   x0 [B][E].  The head's rows of the packed in-projection w_in [3E][E] (+ b_in [3E], nullable)
+ *   give q, k, v; k and v are stored at position t of cache [B][T][2][E] (k, then v; columns
+ *   h * dh ..), which must hold the positions < t of earlier calls; out [B][E] (head-major
+ *   columns, as e2ep_attn_fwd) = softmax(q K^T / sqrt(dh)) V over the positions j <= t with
+ *   seq[b * seq_stride + j] != pad; every key masked: zeros (the e2ep_attn_fwd convention).
+ * e2ep_dec_cross_attn: grid (H, B).  q = (LN(x[b]) w_q^T + b_q) of head h (w_q [E][E]);
+ *   keys / values kv [B][Sk][ldkv], K at column 0 and V at column E (ldkv >= 2E: the memory
+ *   projected by in_proj_weight[E:]); out [B][E] = softmax(q K^T / sqrt(dh)) V, no mask.
+ * e2ep_dec_row_gemv: out[b * ldo + n] = act(sum_k LN(x[b])[k] w[n * K + k] + bias[n])
+ *   + LN_res(res[b])[n] for n < N; bias, res nullable; act = ReLU when relu; the residual's
+ *   LayerNorm (res_gamma, res_beta, res_eps) runs over its N values.  out must not alias x or
+ *   res.
+ * ------------------------------------------------------------------------------------- */
+int e2ep_dec_self_attn(const float *x, int ldx, const float *gamma, const float *beta, float eps,
+                       const float *table, int V, const float *pos, float *x0, const int64_t *seq,
+                       int seq_stride, int64_t pad, const float *w_in, const float *b_in,
+                       float *cache, float *out, int B, int T, int t, int E, int H, void *stream);
+int e2ep_dec_cross_attn(const float *x, int ldx, const float *gamma, const float *beta, float eps,
+                        const float *w_q, const float *b_q, const float *kv, int ldkv, float *out,
+                        int B, int Sk, int E, int H, void *stream);
+int e2ep_dec_row_gemv(const float *x, int ldx, const float *gamma, const float *beta, float eps,
+                      const float *w, const float *bias, const float *res, int ldr,
+                      const float *res_gamma, const float *res_beta, float res_eps, float *out,
+                      int ldo, int B, int N, int K, int relu, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimizer: fused Adam over one flat parameter buffer (replaces torch.optim.Adam configured
  * at trainer/pl_trainer.py:116-121; torch Adam semantics: L2 weight decay added to the
  * gradient, bias-corrected step, no amsgrad).
