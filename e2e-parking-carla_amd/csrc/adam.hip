@@ -5,6 +5,13 @@
 // gradients are either the per-tensor buffers autograd produced (a device table of pointers,
 // so no accumulate-into-flat copy is needed) or one flat buffer (data-parallel: gathered and
 // all-reduced).  One launch updates all ~28M weights: 7 x 4 bytes per weight of HBM traffic.
+//
+// Optional (e2ep_adam_step_clipped): global gradient-norm clipping and skipping of a non-finite
+// step.  k_gnorm_partial (one fp64 sum of squares per chunk-table row) -> k_gnorm_final (one
+// workgroup: norm, clip coefficient, skip flag, all left in device memory) -> k_adam_clip, which
+// reads the coefficient and the flag there: one capturable chain, no host synchronisation, no
+// atomics, the same bits whatever the gradient source or its alignment.  k_grad_accum adds a
+// micro-step's gradients into the flat buffer (gradient accumulation).
 #include "common.h"
 
 namespace e2ep {
@@ -24,13 +31,18 @@ constexpr int ADAM_ITERS = 4;
 
 __global__ void k_adam_count(float *step) { step[0] += 1.f; }
 
-// chunk table row: {tensor, start element within tensor, length, unused}
-__global__ void __launch_bounds__(ADAM_THREADS)
-    k_adam(const int4 *__restrict__ chunks, const long long *__restrict__ offs,
-           const long long *__restrict__ gptrs, const float *__restrict__ gflat,
-           float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
-           const float *__restrict__ step, const double *__restrict__ lr, AdamHyper h,
-           int *__restrict__ stepped) {
+// The update of one chunk-table row {tensor, start element within tensor, length, unused}.
+// CLIP: the gradient is also multiplied by a clip coefficient read from device memory (after
+// grad_scale, before the weight decay), for the launch that follows k_gnorm_final.
+template <bool CLIP>
+__device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
+                                         const long long *__restrict__ offs,
+                                         const long long *__restrict__ gptrs,
+                                         const float *__restrict__ gflat, float *__restrict__ p,
+                                         float *__restrict__ m, float *__restrict__ v,
+                                         const float *__restrict__ step,
+                                         const double *__restrict__ lr, const AdamHyper &h,
+                                         float coef, int *__restrict__ stepped) {
   const int4 c = chunks[blockIdx.x];
   const long long off = offs[c.x] + c.y;
   // a parameter without a gradient this step is not stepped (as torch.optim.Adam); on the
@@ -53,6 +65,7 @@ __global__ void __launch_bounds__(ADAM_THREADS)
   const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;  // wave-uniform
   auto upd = [&](float &pv, float &mv, float &vv, float gv) {
     gv = gv * h.grad_scale;
+    if (CLIP) gv = gv * coef;  // clip_grad_norm_: g.mul_(clip_coef), then Adam's g + wd * p
     gv = gv + h.wd * pv;
     mv = mv + w1 * (gv - mv);  // exp_avg.lerp_(grad, 1 - beta1)
     vv = vv * h.b2f + w2 * gv * gv;
@@ -85,6 +98,109 @@ __global__ void __launch_bounds__(ADAM_THREADS)
   }
 }
 
+__global__ void __launch_bounds__(ADAM_THREADS)
+    k_adam(const int4 *__restrict__ chunks, const long long *__restrict__ offs,
+           const long long *__restrict__ gptrs, const float *__restrict__ gflat,
+           float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
+           const float *__restrict__ step, const double *__restrict__ lr, AdamHyper h,
+           int *__restrict__ stepped) {
+  adam_row<false>(chunks, offs, gptrs, gflat, p, m, v, step, lr, h, 1.f, stepped);
+}
+
+// ---- gradient norm, clip coefficient, skip flag (the launches in front of k_adam_clip) ----
+
+// 256 per-thread fp64 values -> their sum in a fixed order: an xor butterfly inside each
+// 64-lane wave (every lane ends with the same bits), then the four wave sums left to right.
+__device__ __forceinline__ double block_sum_f64(double acc, double *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// One fp64 sum of squares per chunk-table row (0 for a tensor without a gradient).  Products
+// and sums are fp64, so the sum is finite exactly when every value is.  Element j of the row
+// always belongs to thread (j / 4) % 256 and is added in increasing j, whether the gradient is
+// read with 16-byte loads or, from an unaligned address, one float at a time: the partial does
+// not depend on the load width.
+__global__ void __launch_bounds__(ADAM_THREADS)
+    k_gnorm_partial(const int4 *__restrict__ chunks, const long long *__restrict__ offs,
+                    const long long *__restrict__ gptrs, const float *__restrict__ gflat,
+                    double *__restrict__ partial) {
+  __shared__ double red[ADAM_THREADS / 64];
+  const int4 c = chunks[blockIdx.x];
+  const float *gt = gptrs ? reinterpret_cast<const float *>(gptrs[c.x]) : nullptr;
+  if (gptrs && gt == nullptr) {  // block-uniform
+    if (threadIdx.x == 0) partial[blockIdx.x] = 0.0;
+    return;
+  }
+  const float *g = gflat ? gflat + offs[c.x] + c.y : gt + c.y;
+  const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+  double acc = 0.0;
+  auto add = [&](float gv) { acc = acc + (double)gv * (double)gv; };
+#pragma unroll
+  for (int it = 0; it < ADAM_ITERS; ++it) {
+    const int i = (it * ADAM_THREADS + threadIdx.x) * ADAM_VEC;
+    if (i >= c.z) break;
+    if (vec && i + ADAM_VEC <= c.z) {
+      const float4 G = *reinterpret_cast<const float4 *>(g + i);
+      add(G.x);
+      add(G.y);
+      add(G.z);
+      add(G.w);
+    } else {
+      const int e = min(i + ADAM_VEC, c.z);
+      for (int j = i; j < e; ++j) add(g[j]);
+    }
+  }
+  const double s = block_sum_f64(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// One workgroup: thread t adds partials t, t + 256, ... in that order, then block_sum_f64.
+// norm = sqrt(sum) * |grad_scale|; coef = max_norm / (norm + 1e-6) limited to 1 by a compare
+// that lets a NaN through (torch.clamp(max=1.0)), or exactly 1 when max_norm < 0 (clipping
+// off); skip = skip_nonfinite and the norm is not finite; skipped counts the skips.
+__global__ void __launch_bounds__(ADAM_THREADS)
+    k_gnorm_final(const double *__restrict__ partial, int n, double grad_scale, double max_norm,
+                  int skip_nonfinite, double *__restrict__ norm, float *__restrict__ coef,
+                  int *__restrict__ skip, long long *__restrict__ skipped) {
+  __shared__ double red[ADAM_THREADS / 64];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += ADAM_THREADS) acc = acc + partial[i];
+  const double s = block_sum_f64(acc, red);
+  if (threadIdx.x != 0) return;
+  const double nrm = sqrt(s) * fabs(grad_scale);
+  double cf = 1.0;
+  if (max_norm >= 0.0) {
+    cf = max_norm / (nrm + 1e-6);
+    if (cf > 1.0) cf = 1.0;
+  }
+  const int sk = (skip_nonfinite && !isfinite(nrm)) ? 1 : 0;
+  norm[0] = nrm;
+  coef[0] = (float)cf;
+  skip[0] = sk;
+  skipped[0] += sk;
+}
+
+__global__ void k_adam_count_unless(float *step, const int *__restrict__ skip) {
+  if (skip[0] == 0) step[0] += 1.f;
+}
+
+// k_adam with the clip coefficient; a set skip flag leaves parameters, moments and the
+// stepped flags as they are
+__global__ void __launch_bounds__(ADAM_THREADS)
+    k_adam_clip(const int4 *__restrict__ chunks, const long long *__restrict__ offs,
+                const long long *__restrict__ gptrs, const float *__restrict__ gflat,
+                float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
+                const float *__restrict__ step, const double *__restrict__ lr, AdamHyper h,
+                const float *__restrict__ coef, const int *__restrict__ skip,
+                int *__restrict__ stepped) {
+  if (skip[0] != 0) return;
+  adam_row<true>(chunks, offs, gptrs, gflat, p, m, v, step, lr, h, coef[0], stepped);
+}
+
 // gather per-tensor gradients into the flat (aligned, zero-padded) buffer for all-reduce
 __global__ void __launch_bounds__(ADAM_THREADS)
     k_grad_gather(const int4 *__restrict__ chunks, const long long *__restrict__ offs,
@@ -93,6 +209,38 @@ __global__ void __launch_bounds__(ADAM_THREADS)
   const float *g = reinterpret_cast<const float *>(gptrs[c.x]);
   float *o = flat + offs[c.x] + c.y;
   for (int j = threadIdx.x; j < c.z; j += ADAM_THREADS) o[j] = g ? g[c.y + j] : 0.f;
+}
+
+// flat[off + j] += g[j] over the chunk table (gradient accumulation; a tensor without a
+// gradient adds nothing).  One add per element, so the load width does not change the result.
+__global__ void __launch_bounds__(ADAM_THREADS)
+    k_grad_accum(const int4 *__restrict__ chunks, const long long *__restrict__ offs,
+                 const long long *__restrict__ gptrs, float *__restrict__ flat) {
+  const int4 c = chunks[blockIdx.x];
+  const float *gt = reinterpret_cast<const float *>(gptrs[c.x]);
+  if (gt == nullptr) return;
+  const float *g = gt + c.y;
+  float *o = flat + offs[c.x] + c.y;  // 16-byte aligned: offsets and row starts are multiples of 4
+  if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+#pragma unroll
+    for (int it = 0; it < ADAM_ITERS; ++it) {
+      const int i = (it * ADAM_THREADS + threadIdx.x) * ADAM_VEC;
+      if (i >= c.z) break;
+      if (i + ADAM_VEC <= c.z) {
+        float4 O = *reinterpret_cast<const float4 *>(o + i);
+        const float4 G = *reinterpret_cast<const float4 *>(g + i);
+        O.x += G.x;
+        O.y += G.y;
+        O.z += G.z;
+        O.w += G.w;
+        *reinterpret_cast<float4 *>(o + i) = O;
+      } else {
+        for (int j = i; j < c.z; ++j) o[j] += g[j];
+      }
+    }
+  } else {
+    for (int j = threadIdx.x; j < c.z; j += ADAM_THREADS) o[j] += g[j];
+  }
 }
 
 }  // namespace e2ep
@@ -127,6 +275,58 @@ int e2ep_grad_gather(const int *chunks, int n_chunks, const long long *offsets,
   hipLaunchKernelGGL(k_grad_gather, dim3(n_chunks), dim3(ADAM_THREADS), 0, as_stream(stream),
                      reinterpret_cast<const int4 *>(chunks), offsets, grad_ptrs, grad_flat);
   return launch_status("e2ep_grad_gather");
+}
+
+int e2ep_grad_sqnorm(const int *chunks, int n_chunks, const long long *offsets,
+                     const long long *grad_ptrs, const float *grad_flat, double *partials,
+                     void *stream) {
+  E2EP_REQUIRE(n_chunks > 0 && chunks && offsets && partials, E2EP_EINVAL,
+               "e2ep_grad_sqnorm: null argument");
+  E2EP_REQUIRE(grad_ptrs || grad_flat, E2EP_EINVAL, "e2ep_grad_sqnorm: no gradients");
+  hipLaunchKernelGGL(k_gnorm_partial, dim3(n_chunks), dim3(ADAM_THREADS), 0, as_stream(stream),
+                     reinterpret_cast<const int4 *>(chunks), offsets, grad_ptrs, grad_flat,
+                     partials);
+  return launch_status("e2ep_grad_sqnorm");
+}
+
+int e2ep_grad_norm_finalize(const double *partials, int n_chunks, float grad_scale,
+                            double max_norm, int skip_nonfinite, double *norm, float *clip_coef,
+                            int *skip, long long *skipped, void *stream) {
+  E2EP_REQUIRE(n_chunks > 0 && partials && norm && clip_coef && skip && skipped, E2EP_EINVAL,
+               "e2ep_grad_norm_finalize: null argument");
+  E2EP_REQUIRE(max_norm == max_norm, E2EP_EINVAL, "e2ep_grad_norm_finalize: max_norm is NaN");
+  hipLaunchKernelGGL(k_gnorm_final, dim3(1), dim3(ADAM_THREADS), 0, as_stream(stream), partials,
+                     n_chunks, (double)grad_scale, max_norm, skip_nonfinite, norm, clip_coef, skip,
+                     skipped);
+  return launch_status("e2ep_grad_norm_finalize");
+}
+
+int e2ep_adam_step_clipped(const int *chunks, int n_chunks, const long long *offsets,
+                           const long long *grad_ptrs, const float *grad_flat, float *param,
+                           float *exp_avg, float *exp_avg_sq, float *step, const double *lr,
+                           double beta1, double beta2, double eps, double weight_decay,
+                           float grad_scale, const float *clip_coef, const int *skip,
+                           int *stepped, void *stream) {
+  E2EP_REQUIRE(n_chunks > 0 && chunks && offsets && param && exp_avg && exp_avg_sq && step && lr &&
+                   clip_coef && skip,
+               E2EP_EINVAL, "e2ep_adam_step_clipped: null argument");
+  E2EP_REQUIRE(grad_ptrs || grad_flat, E2EP_EINVAL, "e2ep_adam_step_clipped: no gradients");
+  AdamHyper h{beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+              (float)(1.0 - beta2), (float)eps, (float)weight_decay, grad_scale};
+  hipLaunchKernelGGL(k_adam_count_unless, dim3(1), dim3(1), 0, as_stream(stream), step, skip);
+  hipLaunchKernelGGL(k_adam_clip, dim3(n_chunks), dim3(ADAM_THREADS), 0, as_stream(stream),
+                     reinterpret_cast<const int4 *>(chunks), offsets, grad_ptrs, grad_flat, param,
+                     exp_avg, exp_avg_sq, step, lr, h, clip_coef, skip, stepped);
+  return launch_status("e2ep_adam_step_clipped");
+}
+
+int e2ep_grad_accumulate(const int *chunks, int n_chunks, const long long *offsets,
+                         const long long *grad_ptrs, float *grad_flat, void *stream) {
+  E2EP_REQUIRE(n_chunks > 0 && chunks && offsets && grad_ptrs && grad_flat, E2EP_EINVAL,
+               "e2ep_grad_accumulate: null argument");
+  hipLaunchKernelGGL(k_grad_accum, dim3(n_chunks), dim3(ADAM_THREADS), 0, as_stream(stream),
+                     reinterpret_cast<const int4 *>(chunks), offsets, grad_ptrs, grad_flat);
+  return launch_status("e2ep_grad_accumulate");
 }
 
 }  // extern "C"

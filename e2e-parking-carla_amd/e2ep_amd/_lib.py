@@ -119,6 +119,11 @@ SIGNATURES = {
     "e2ep_adam_chunk_elems": (_i, []),
     "e2ep_adam_step": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _f, _p, _p]),
     "e2ep_grad_gather": (_i, [_p, _i, _p, _p, _p, _p]),
+    "e2ep_grad_sqnorm": (_i, [_p, _i, _p, _p, _p, _p, _p]),
+    "e2ep_grad_norm_finalize": (_i, [_p, _i, _f, _d, _i, _p, _p, _p, _p, _p]),
+    "e2ep_adam_step_clipped": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _f,
+                                    _p, _p, _p, _p]),
+    "e2ep_grad_accumulate": (_i, [_p, _i, _p, _p, _p, _p]),
     "e2ep_graph_replace_memsets": (_i, [_p, ctypes.POINTER(_i)]),
     "e2ep_graph_exec_create": (_i, [_p, _p]),
     "e2ep_graph_exec_launch": (_i, [_p, _p]),

@@ -20,6 +20,26 @@ reference never changes them).
 
 state_dict() / load_state_dict() use torch.optim.Adam's format, so checkpoints move
 between this optimizer and the reference's.
+
+Optional, all off by default (step() then makes exactly the calls it always made):
+  * max_grad_norm: global gradient-norm clipping, torch.nn.utils.clip_grad_norm_'s formula
+    (Lightning's gradient_clip_val).  step() becomes three entry-point calls, four kernel
+    launches, in one capturable chain: one fp64 sum of squares per chunk-table row
+    (k_gnorm_partial), one workgroup that sums them in a fixed order and writes the norm, the
+    clip coefficient and a skip flag to device memory (k_gnorm_final), and the step counter and
+    Adam launches that read the coefficient and the flag there (k_adam_count_unless,
+    k_adam_clip).  No host synchronisation: the norm
+    (`grad_norm_dev`, float64, before clipping), `clip_coef_dev` and `skipped_dev` are
+    persistent device tensors, and reading them is the caller's synchronisation.  The norm is
+    reproducible bit for bit: it does not depend on the gradient source (table or flat
+    buffer), on a gradient's alignment, or on eager launch versus graph replay.
+  * skip_nonfinite: an update whose gradient norm is Inf or NaN changes nothing (parameters,
+    moments, step counter, stepped flags) and is counted in `skipped_dev`.
+  * accumulate_grads(flat, first) / has_grad(out, union=True): gradient accumulation into a
+    flat buffer over several micro-steps (Lightning's accumulate_grad_batches), followed by
+    step(flat, 1 / micro_steps, has_grad=union).
+The two settings are attributes and no optimizer state (state_dict() does not carry them); a
+captured step keeps the values it was captured with.
 """
 import torch
 
@@ -29,7 +49,8 @@ _ALIGN = 4  # elements (16 bytes)
 
 
 class FlatAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 max_grad_norm=None, skip_nonfinite=False):
         params = list(params)
         if not params:
             raise ValueError("FlatAdam: empty parameter list")
@@ -84,6 +105,16 @@ class FlatAdam(torch.optim.Optimizer):
             r += n
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float64, device=dev)
         self._lr_written = float(lr)
+        # gradient-norm clipping / non-finite skip (module docstring): settings, the device
+        # scalars the chain writes, and its workspace (one fp64 partial per chunk-table row)
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.grad_norm_dev = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.clip_coef_dev = torch.ones(1, dtype=torch.float32, device=dev)
+        self.skipped_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._skip_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._partials = torch.zeros(self.n_chunks, dtype=torch.float64, device=dev)
+        self._has_i64 = torch.zeros(len(self.params), dtype=torch.int64, device=dev)
 
     # -- learning rate ------------------------------------------------------------------------
     @property
@@ -142,14 +173,33 @@ class FlatAdam(torch.optim.Optimizer):
         _lib.call("e2ep_grad_gather", ctypes.c_void_p(self.chunks.data_ptr() + 16 * r0), r1 - r0,
                   _lib.ptr(self.offsets), _lib.ptr(self._gtab), _lib.ptr(out), _lib.stream())
 
+    def accumulate_grads(self, flat, first):
+        """One micro-step of gradient accumulation into `flat` (parameter layout), from the
+        prepared table: the first micro-step of a cycle gathers (zeros for a tensor without a
+        gradient, so `flat` needs no clearing), every later one adds (such a tensor adds
+        nothing).  Pair it with has_grad(out, union=not first), then
+        step(flat, 1 / micro_steps, has_grad=out)."""
+        if first:
+            self.gather_grads(flat)
+            return
+        _lib.call("e2ep_grad_accumulate", _lib.ptr(self.chunks), self.n_chunks,
+                  _lib.ptr(self.offsets), _lib.ptr(self._gtab), _lib.ptr(flat), _lib.stream())
+
     # -- update -----------------------------------------------------------------------------
     @torch.no_grad()
-    def has_grad(self, out):
+    def has_grad(self, out, union=False):
         """out[i] = 1 if parameter i has a gradient this step (from the prepared table), else 0
         (int64, capturable).  Data-parallel callers all-reduce it with MAX and pass it to
-        step(grad_flat, ..., has_grad=out): every replica then steps the same parameters."""
+        step(grad_flat, ..., has_grad=out): every replica then steps the same parameters.
+        union=True keeps the entries `out` already has (out[i] = max(out[i], this step's)): over
+        an accumulation cycle a parameter with a gradient in any micro-step is stepped, one
+        with none in the whole cycle is not."""
         torch.ne(self._gtab, 0, out=self._has_bool)
-        out.copy_(self._has_bool)
+        if union:
+            self._has_i64.copy_(self._has_bool)
+            torch.maximum(out, self._has_i64, out=out)
+        else:
+            out.copy_(self._has_bool)
         return out
 
     def step(self, grad_flat=None, grad_scale=1.0, closure=None, has_grad=None):
@@ -158,7 +208,10 @@ class FlatAdam(torch.optim.Optimizer):
         (no gradient) are skipped either way.  With `grad_flat`, `has_grad` (int64 per
         parameter, non-zero = step it; see has_grad()) replaces this rank's own table, so a
         parameter that had a gradient on any rank is stepped on every rank, as under DDP.
-        torch.optim-style calls (no arguments, or a closure) prepare the table themselves."""
+        torch.optim-style calls (no arguments, or a closure) prepare the table themselves.
+        With max_grad_norm or skip_nonfinite set, the norm of the scaled gradient is taken
+        first and the update reads the clip coefficient and the skip flag from device memory
+        (module docstring); the norm is over the tensors that are stepped."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -167,13 +220,34 @@ class FlatAdam(torch.optim.Optimizer):
             self.prepare()
         self.sync_lr()
         b1, b2 = self.betas
-        _lib.call("e2ep_adam_step", _lib.ptr(self.chunks), self.n_chunks, _lib.ptr(self.offsets),
-                  _lib.ptr(has_grad if (has_grad is not None and grad_flat is not None)
-                           else self._gtab),
-                  _lib.ptr(grad_flat) if grad_flat is not None else None,
+        table = _lib.ptr(has_grad if (has_grad is not None and grad_flat is not None)
+                         else self._gtab)
+        gflat = _lib.ptr(grad_flat) if grad_flat is not None else None
+        if self.max_grad_norm is None and not self.skip_nonfinite:
+            _lib.call("e2ep_adam_step", _lib.ptr(self.chunks), self.n_chunks,
+                      _lib.ptr(self.offsets), table, gflat,
+                      _lib.ptr(self.flat), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                      _lib.ptr(self.step_count), _lib.ptr(self.lr_dev), float(b1), float(b2),
+                      float(self.eps), float(self.weight_decay), float(grad_scale),
+                      _lib.ptr(self.stepped), _lib.stream())
+            return loss
+        max_norm = -1.0  # the finalisation's "clipping off": the coefficient is exactly 1
+        if self.max_grad_norm is not None:
+            max_norm = float(self.max_grad_norm)
+            if not max_norm >= 0.0:
+                raise ValueError(f"FlatAdam: max_grad_norm must be >= 0, got {self.max_grad_norm}")
+        _lib.call("e2ep_grad_sqnorm", _lib.ptr(self.chunks), self.n_chunks, _lib.ptr(self.offsets),
+                  table, gflat, _lib.ptr(self._partials), _lib.stream())
+        _lib.call("e2ep_grad_norm_finalize", _lib.ptr(self._partials), self.n_chunks,
+                  float(grad_scale), max_norm, int(self.skip_nonfinite),
+                  _lib.ptr(self.grad_norm_dev), _lib.ptr(self.clip_coef_dev),
+                  _lib.ptr(self._skip_dev), _lib.ptr(self.skipped_dev), _lib.stream())
+        _lib.call("e2ep_adam_step_clipped", _lib.ptr(self.chunks), self.n_chunks,
+                  _lib.ptr(self.offsets), table, gflat,
                   _lib.ptr(self.flat), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
                   _lib.ptr(self.step_count), _lib.ptr(self.lr_dev), float(b1), float(b2),
                   float(self.eps), float(self.weight_decay), float(grad_scale),
+                  _lib.ptr(self.clip_coef_dev), _lib.ptr(self._skip_dev),
                   _lib.ptr(self.stepped), _lib.stream())
         return loss
 

@@ -40,6 +40,18 @@ without its module wrapper), one flat fp32 gradient buffer in FlatAdam's layout;
     HIP streams, so the flat buffer is staged explicitly through pinned host memory (copy,
     the host waits for the stream, all-reduce on the host, copy back).
 
+Gradient-norm clipping, skipping a non-finite update and gradient accumulation
+(TrainStep(max_grad_norm=, skip_nonfinite=, accumulate=); Lightning's gradient_clip_val and
+accumulate_grad_batches) are FlatAdam's (optim.py): the norm, the clip coefficient and the
+skip decision are computed and consumed on the device inside the optimizer graph, after the
+all-reduce and over the averaged gradient, so every rank takes the same decision and the step
+stays a chain of replays without a host synchronisation.  They act in _update, hence on every
+exchange path above.  With accumulate = A > 1 every call is one micro-step: the backward
+graph, then a gather graph (first micro-step of a cycle: it overwrites the flat buffer, no
+memset) or an accumulate graph (later ones); every A-th call also runs ONE exchange of the
+accumulated buffer — the non-overlapped, non-segmented path: no hook buckets, no segments —
+and the optimizer graph with 1 / (A * world) folded into the Adam launch.
+
 Graphs are captured through e2ep_amd.graphs.capture, which repairs memset nodes (they do
 not replay correctly on this ROCm stack) before instantiation.
 
@@ -175,9 +187,30 @@ class GradBuckets:
 
 
 class TrainStep:
+    """One (micro-)step per call; see the module docstring for the paths.
+
+    max_grad_norm / skip_nonfinite / accumulate: an explicit value (a number, True / False, a
+    count) wins; None falls back to module.cfg's gradient_clip_val / skip_nonfinite_steps /
+    accumulate_grad_batches when the module has them, and then to what a passed-in FlatAdam
+    already has (off for the optimizer TrainStep builds itself; accumulate 1).  The resolved
+    clipping and skip settings are written to the FlatAdam as attributes before the capture.
+    None is the "not given" value, so max_grad_norm=None cannot switch off a clip value that
+    the config or the passed-in optimizer carries: clear it there (cfg.gradient_clip_val,
+    optimizer.max_grad_norm = None) before building the TrainStep.  skip_nonfinite=False does
+    switch the skip off.  With all three off the object captures the same graphs and issues
+    the same launches as without them.  An option that is on needs a FlatAdam (ValueError
+    otherwise).
+    Every call is one micro-step and returns that micro-batch's loss, the warm-up calls a
+    graph-mode constructor makes on its construction batch included; every accumulate-th
+    call also updates, with the gradient mean 1 / (accumulate * world) folded into the Adam
+    launch.  With accumulate > 1 and data parallelism the exchange happens once per cycle, on
+    the accumulated buffer, over the non-overlapped, non-segmented path: `segmented` is False
+    and `buckets` is None whatever `segment` / `overlap` say.  `grad_norm` is the device
+    scalar holding the last update's norm before clipping."""
+
     def __init__(self, module, batch, lr=1e-4, weight_decay=1e-4, world=1, graph=True,
                  warmup=3, optimizer=None, bucket_mb=BUCKET_MB, overlap=None, ddp=None,
-                 segment=True):
+                 segment=True, max_grad_norm=None, skip_nonfinite=None, accumulate=None):
         self.module = module
         self.batch = batch
         self.world = world
@@ -188,21 +221,47 @@ class TrainStep:
         self.params = [p for p in module.parameters() if p.requires_grad]
         self.opt = optimizer if optimizer is not None else FlatAdam(
             self.params, lr=lr, weight_decay=weight_decay)
+        # clipping / non-finite skip / accumulation (class docstring): an explicit argument
+        # wins, None falls back to module.cfg's Lightning-named keys, then to what the
+        # optimizer already has
+        cfg = getattr(module, "cfg", None)
+        skip_given = skip_nonfinite is not None
+        if max_grad_norm is None:
+            max_grad_norm = getattr(cfg, "gradient_clip_val", None)
+        if not skip_given:
+            skip_nonfinite = getattr(cfg, "skip_nonfinite_steps", None)
+        if accumulate is None:
+            accumulate = getattr(cfg, "accumulate_grad_batches", None)
+        self.accumulate = 1 if accumulate is None else int(accumulate)
+        if self.accumulate < 1:
+            raise ValueError(f"TrainStep: accumulate must be >= 1, got {accumulate}")
+        if isinstance(self.opt, FlatAdam):
+            if max_grad_norm is not None:
+                self.opt.max_grad_norm = float(max_grad_norm)
+            if skip_given or skip_nonfinite:
+                self.opt.skip_nonfinite = bool(skip_nonfinite)
+        elif max_grad_norm is not None or skip_nonfinite or self.accumulate > 1:
+            raise ValueError("TrainStep: max_grad_norm, skip_nonfinite and accumulate need a "
+                             "FlatAdam optimizer")
+        self._micro = 0  # position in the accumulation cycle
         dev = self.params[0].device
+        flat = self.ddp or self.accumulate > 1
         self.flat_grad = (torch.zeros(self.opt.numel, dtype=torch.float32, device=dev)
-                          if self.ddp else None)
+                          if flat else None)
         # which parameters had a gradient on ANY rank (all-reduced MAX with the gradients):
         # every replica steps the same set, as under DDP (a rank-local mask lets
-        # replicas drift when a branch is rank-dependent)
+        # replicas drift when a branch is rank-dependent); over an accumulation cycle, in any
+        # micro-step
         self.has_grad = (torch.zeros(len(self.params), dtype=torch.int64, device=dev)
-                         if self.ddp else None)
+                         if flat else None)
         self.backend = dist.get_backend() if self.ddp else None
         if overlap is None:
             overlap = os.environ.get("E2EP_DDP_OVERLAP", "1") != "0"
         # hook-driven bucket all-reduce overlapping backward: eager steps with RCCL, and host
-        # tensors (gloo on CPU); never inside a captured graph (module docstring)
+        # tensors (gloo on CPU); never inside a captured graph (module docstring), and not
+        # with accumulation (one exchange per cycle, on the accumulated buffer)
         self._bucket_mb = bucket_mb
-        self.overlap = bool(self.ddp and overlap and not graph and
+        self.overlap = bool(self.ddp and overlap and not graph and self.accumulate == 1 and
                             (self.backend == "nccl" or not self.flat_grad.is_cuda))
         self.buckets = (GradBuckets(self.params, self.opt, self.flat_grad, bucket_mb)
                         if self.overlap else None)
@@ -212,10 +271,11 @@ class TrainStep:
                       if self.ddp and self.backend != "nccl" and not self.overlap
                       and self.flat_grad.is_cuda else None)
         self.loss = None
-        self.g_bwd = self.g_gather = self.g_opt = None
+        self.g_bwd = self.g_gather = self.g_acc = self.g_opt = None
         # segmented backward (graph mode; RCCL, or gloo staged through self._host): stage
-        # graphs, their gathers, bucket ranges.  segment=False keeps one backward graph.
-        self.segmented = bool(segment and self.ddp and graph and
+        # graphs, their gathers, bucket ranges.  segment=False keeps one backward graph, and
+        # so does accumulation.
+        self.segmented = bool(segment and self.ddp and graph and self.accumulate == 1 and
                               (self.backend == "nccl" or self._host is not None))
         self.g_s1 = self.g_s1g = self.g_s2 = self.g_s2g = None
         self.seg_buckets = None  # ([stage-1 (lo, hi)], [stage-2 (lo, hi)]) of the flat buffer
@@ -268,14 +328,29 @@ class TrainStep:
         self.has_grad.copy_(has, non_blocking=True)
 
     def _update(self):
-        if self.ddp:
-            self.opt.step(self.flat_grad, 1.0 / self.world, has_grad=self.has_grad)
+        if self.flat_grad is not None:
+            self.opt.step(self.flat_grad, 1.0 / (self.world * self.accumulate),
+                          has_grad=self.has_grad)
         else:
             self.opt.step()
+
+    def _accumulate(self, first):
+        """One micro-step's gradients into the flat buffer: gathered by the first micro-step of
+        a cycle, added by the later ones; has_grad becomes the union over the cycle."""
+        self.opt.accumulate_grads(self.flat_grad, first)
+        self.opt.has_grad(self.has_grad, union=not first)
 
     def _eager(self):
         loss = self._fwd_bwd()
         self.opt.prepare()
+        if self.accumulate > 1:
+            k = self._micro
+            self._accumulate(k == 0)
+            if k == self.accumulate - 1:
+                self._allreduce()
+                self._update()
+            self._micro = (k + 1) % self.accumulate
+            return loss
         self._gather()
         self._allreduce()
         self._update()
@@ -438,12 +513,19 @@ class TrainStep:
         self.g_bwd, self.loss, self.memsets = graphs.capture(self._fwd_bwd)
         # the captured gradients keep their (graph-pool) addresses on every replay
         self.opt.prepare()
-        if self.ddp and self.buckets is None:
+        if self.accumulate > 1:
+            self.g_gather, _, _ = graphs.capture(lambda: self._accumulate(True),
+                                                 pool=self.g_bwd.pool())
+            self.g_acc, _, _ = graphs.capture(lambda: self._accumulate(False),
+                                              pool=self.g_bwd.pool())
+        elif self.ddp and self.buckets is None:
             self.g_gather, _, _ = graphs.capture(self._gather, pool=self.g_bwd.pool())
         self.g_opt, _, _ = graphs.capture(self._update, pool=self.g_bwd.pool())
 
     def __call__(self, batch=None):
-        """One training step; `batch` (optional) is copied into the captured input buffers."""
+        """One micro-step (with accumulate == 1: one training step); `batch` (optional) is
+        copied into the captured input buffers.  Returns this micro-batch's loss; every
+        `accumulate`-th call also runs the exchange and the update."""
         if batch is not None:
             if self.graph and _rig_key(batch) != self._rig:
                 raise _lib.E2EPError(
@@ -463,8 +545,22 @@ class TrainStep:
             self._replay_segmented()
             return self.loss
         self.g_bwd.replay()
+        if self.accumulate > 1:
+            k = self._micro
+            (self.g_gather if k == 0 else self.g_acc).replay()
+            if k == self.accumulate - 1:
+                self._allreduce()
+                self.g_opt.replay()
+            self._micro = (k + 1) % self.accumulate
+            return self.loss
         if self.g_gather is not None:
             self.g_gather.replay()
             self._allreduce()
         self.g_opt.replay()
         return self.loss
+
+    @property
+    def grad_norm(self):
+        """The last update's gradient norm before clipping (a float64 device scalar written by
+        the optimizer chain when clipping or skipping is on; reading it synchronises)."""
+        return self.opt.grad_norm_dev

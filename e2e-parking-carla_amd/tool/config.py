@@ -4,6 +4,9 @@
 `parking_model` section.  The device defaults to the HIP device (`cuda` on PyTorch-ROCm).
 Optional MI355X keys (absent from reference configs, defaults shown):
   deterministic: False   zero every dropout / drop-connect (SURVEY.md §8c protocol)
+  gradient_clip_val: None       global gradient-norm clipping (Lightning's Trainer argument)
+  accumulate_grad_batches: 1    micro-batches per optimizer update (Lightning's Trainer argument)
+  skip_nonfinite_steps: False   leave out an update whose gradient norm is Inf or NaN
 """
 import os
 from datetime import datetime
@@ -27,6 +30,9 @@ class Configuration:
     log_dir = None
     checkpoint_dir = None
     deterministic = False
+    gradient_clip_val = None
+    accumulate_grad_batches = 1
+    skip_nonfinite_steps = False
 
 
 for _k in _KEYS:
@@ -43,6 +49,10 @@ def get_cfg(cfg_yaml: dict) -> Configuration:
     for k in _KEYS:
         setattr(cfg, k, section[k])
     cfg.deterministic = bool(section.get("deterministic", False))
+    clip = section.get("gradient_clip_val")
+    cfg.gradient_clip_val = None if clip is None else float(clip)
+    cfg.accumulate_grad_batches = int(section.get("accumulate_grad_batches", 1))
+    cfg.skip_nonfinite_steps = bool(section.get("skip_nonfinite_steps", False))
     return cfg
 
 

@@ -92,9 +92,37 @@ class ParkingTrainingModule(_Base):
         params = [p for p in self.parameters() if p.requires_grad]
         if params and params[0].is_cuda:
             from e2ep_amd.optim import FlatAdam
-            opt = FlatAdam(params, lr=self.cfg.learning_rate, weight_decay=self.cfg.weight_decay)
+            opt = FlatAdam(params, lr=self.cfg.learning_rate, weight_decay=self.cfg.weight_decay,
+                           max_grad_norm=getattr(self.cfg, "gradient_clip_val", None),
+                           skip_nonfinite=getattr(self.cfg, "skip_nonfinite_steps", False))
         else:
             opt = torch.optim.Adam(params, lr=self.cfg.learning_rate,
                                    weight_decay=self.cfg.weight_decay)
         sched = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer=opt, T_max=self.cfg.epochs)
         return {"optimizer": opt, "lr_scheduler": sched}
+
+    def configure_gradient_clipping(self, optimizer, *args, gradient_clip_val=None,
+                                    gradient_clip_algorithm=None, **kw):
+        """Lightning's hook for Trainer(gradient_clip_val=...) (1.x passes an extra positional
+        optimizer_idx, 2.x none).  For the fused flat Adam and clipping by norm it only sets
+        optimizer.max_grad_norm: the following optimizer.step() takes the norm and clips
+        inside its own launches, and torch does not clip a second time.  Anything else goes to
+        Lightning's default when Lightning is there, else to torch.nn.utils."""
+        algo = getattr(gradient_clip_algorithm, "value", gradient_clip_algorithm)  # str or enum
+        by_norm = algo is None or str(algo).lower() == "norm"
+        flat = getattr(optimizer, "_optimizer", optimizer)  # through a LightningOptimizer wrapper
+        if by_norm and hasattr(flat, "max_grad_norm"):  # FlatAdam's setting
+            if gradient_clip_val is not None:
+                flat.max_grad_norm = float(gradient_clip_val)
+            return
+        if HAVE_PL:  # pragma: no cover - PL absent in this image
+            return super().configure_gradient_clipping(
+                optimizer, *args, gradient_clip_val=gradient_clip_val,
+                gradient_clip_algorithm=gradient_clip_algorithm, **kw)
+        if gradient_clip_val is None:
+            return
+        params = [p for g in optimizer.param_groups for p in g["params"]]
+        if by_norm:
+            torch.nn.utils.clip_grad_norm_(params, float(gradient_clip_val))
+        else:
+            torch.nn.utils.clip_grad_value_(params, float(gradient_clip_val))

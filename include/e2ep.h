@@ -731,6 +731,41 @@ int e2ep_adam_step(const int *chunks, int n_chunks, const long long *offsets,
  * a sub-range of the chunk table (chunks + 4*first, n) gathers one gradient bucket */
 int e2ep_grad_gather(const int *chunks, int n_chunks, const long long *offsets,
                      const long long *grad_ptrs, float *grad_flat, void *stream);
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, Lightning's
+ * gradient_clip_val), skipping of a non-finite step and gradient accumulation (Lightning's
+ * accumulate_grad_batches) for the flat Adam, as one capturable chain without a host
+ * synchronisation: every scalar the chain decides on stays in device memory.
+ *  - e2ep_grad_sqnorm: partials[row] = fp64 sum of squares of the gradient values of chunk
+ *    table row `row` (n_chunks doubles; 0 for a tensor whose grad_ptrs entry is null); the
+ *    gradient source rules are e2ep_adam_step's.  Products and sums are fp64, so the sum is
+ *    finite exactly when every value is; the summation order depends on the element index
+ *    only (not on the alignment of the gradient), one workgroup per row, no atomics.
+ *  - e2ep_grad_norm_finalize: one workgroup sums the partials in a fixed order and writes
+ *    norm[0] = sqrt(sum) * |grad_scale| (the norm of the scaled gradient before clipping, as
+ *    clip_grad_norm_ returns it), clip_coef[0] = min(max_norm / (norm + 1e-6), 1) with
+ *    torch.clamp's NaN behaviour (a NaN norm gives a NaN coefficient) or exactly 1 when
+ *    max_norm < 0 (clipping off), skip[0] = (skip_nonfinite and norm is Inf or NaN), and
+ *    skipped[0] += skip[0].
+ *  - e2ep_adam_step_clipped: e2ep_adam_step with the gradient formed in fp32 as
+ *    (g * grad_scale) * clip_coef[0] + weight_decay * p.  When skip[0] is set the call changes
+ *    nothing: parameters, moments, the step counter and `stepped` stay as they are.
+ *  - e2ep_grad_accumulate: grad_flat[offset + j] += gradient[j] over the chunk table (a null
+ *    grad_ptrs entry adds nothing).  The first micro-step of a cycle uses e2ep_grad_gather,
+ *    which writes zeros for missing gradients, so the buffer needs no memset. */
+int e2ep_grad_sqnorm(const int *chunks, int n_chunks, const long long *offsets,
+                     const long long *grad_ptrs, const float *grad_flat, double *partials,
+                     void *stream);
+int e2ep_grad_norm_finalize(const double *partials, int n_chunks, float grad_scale,
+                            double max_norm, int skip_nonfinite, double *norm, float *clip_coef,
+                            int *skip, long long *skipped, void *stream);
+int e2ep_adam_step_clipped(const int *chunks, int n_chunks, const long long *offsets,
+                           const long long *grad_ptrs, const float *grad_flat, float *param,
+                           float *exp_avg, float *exp_avg_sq, float *step, const double *lr,
+                           double beta1, double beta2, double eps, double weight_decay,
+                           float grad_scale, const float *clip_coef, const int *skip,
+                           int *stepped, void *stream);
+int e2ep_grad_accumulate(const int *chunks, int n_chunks, const long long *offsets,
+                         const long long *grad_ptrs, float *grad_flat, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Training losses (fp32; fixed-order reductions; every scalar stays on the device):
