@@ -1,5 +1,8 @@
-// Internal interface shared by the convolution kernel files (conv.hip, conv_lp.hip).
+// Internal interface shared by the convolution kernel files (conv.hip, conv_lp.hip,
+// conv_stem.hip).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace e2ep {
@@ -62,41 +65,70 @@ struct TapList {
   int tap[MAXTAPS];
 };
 
+// Host-side template dispatch: a launcher turns a runtime choice into template arguments by
+// calling a generic lambda with integral constants (constexpr int V = decltype(v)::value).
+template <int V> using IntC = std::integral_constant<int, V>;
+// f(IntC<I>, IntC<J>), I / J = 2 where i2 / j2, else 1: the 2 x 2 tile choices of k_wgrad_1x1
+// (32- / 64-row wave tiles) and k_wgrad_lp (64- / 128-row tiles)
+template <class F> inline void with_tile2x2(bool i2, bool j2, F f) {
+  if (i2 && j2) f(IntC<2>(), IntC<2>());
+  else if (i2) f(IntC<2>(), IntC<1>());
+  else if (j2) f(IntC<1>(), IntC<2>());
+  else f(IntC<1>(), IntC<1>());
+}
+
+// Launch plan of a weight gradient (conv.hip wgrad_plan: the one place that picks the kernel).
+// Every kernel writes partial slabs part[split][Cout][Cin*R*S] for the fixed-order split
+// reduction and accepts any splits >= 1 as a cap.
+enum WgradKind { WGRAD_STEM, WGRAD_LP, WGRAD_1X1, WGRAD_GEN2, WGRAD_GEN1 };
+struct WgradPlan {
+  int kind;
+  int op;      // operands: 1 bf16 (C3), 0 fp32 (conv.hip wgrad_op)
+  int tm, tn;  // tile rows (Cout) x columns ((ci, live tap); k_wgrad_1x1: ci)
+  int kstep;   // pixels per K-step (k_wgrad_1x1: its 8-pixel groups)
+  int splits;  // default slab count (e2ep_conv_wgrad_splits)
+  TapList tl;  // live taps
+};
+// a caller's splits -> per: pixels (k_wgrad_1x1: groups) per slab, used: slabs written
+struct WgradGrid { int per, used; };
+
 // Implicit-GEMM forward (mode 0) / data gradient (mode 1) with 32-deep K-steps and up to
 // 128-row tiles, conv_lp.hip: bf16 / fp16 operands (op 1 / 2), and fp32 (op 0) where
-// TUNE_LP32 selects it.  lp_workspace() bytes of split-K workspace (0: none); lp_launch() returns an
-// E2EP status.  Tap-major weights ([R*S][Cout][Cin]) or 1x1 filters only.
+// TUNE_LP32 selects it.  Tap-major weights ([R*S][Cout][Cin]) or 1x1 filters only.
+struct LpPlan {
+  int wm, wn, lk, splits, kper, nph;  // wave tiles (64 rows / columns each), K-step, K split
+  long long ncols;                    // columns of the largest phase
+};
 bool lp_ok(int mode, const ConvGeom &g, int M, int op);
-size_t lp_workspace(int mode, const ConvGeom &g, int M, int op);
+LpPlan lp_plan(int mode, const ConvGeom &g, int M, int op);
+// lp_launch returns an E2EP status.  workspace: splits * M * ncols floats when p.splits > 1.
 // stats (forward only): BatchNorm partial sums of dst from the epilogue (bnstats.h), over
-// lp_stats_tiles(g, op) column tiles (0 = the plan cannot produce them).
+// cdiv(ncols, 64 * wn) column tiles.
 // io (e2ep.h E2EP_IO_*, op 1 only): mode 0 with E2EP_IO_X_BF16 reads a bf16 src, mode 1 with
 // E2EP_IO_DX_BF16 writes a bf16 dst (dst_bytes: its size in bytes); E2EP_EINVAL otherwise.
 int lp_launch(int mode, int act, int op, const float *w, const void *src, const float *bias,
-              void *dst, long long dst_bytes, const ConvGeom &g, int M, void *workspace,
-              hipStream_t s, double *stats = nullptr, int io = 0);
-int lp_stats_tiles(const ConvGeom &g, int op);
+              void *dst, long long dst_bytes, const ConvGeom &g, int M, const LpPlan &p,
+              void *workspace, hipStream_t s, double *stats = nullptr, int io = 0);
 
 // Weight gradient with 32-pixel K-steps and up to 128 x 128 tiles, conv_lp.hip: bf16 operands
-// (op 1, C3) or fp32 (op 0, where TUNE_LP32W selects it).  Partial slabs
-// part[split][Cout][Cin*R*S] for the fixed-order split reduction of conv.hip;
-// lp_wgrad_launch returns the slabs written.
+// (op 1, C3) or fp32 (op 0, where TUNE_LP32W selects it).  lp_wgrad_plan fills p's tile, K-step
+// and default splits from p.op and p.tl.
 bool lp_wgrad_ok(const ConvGeom &g, const TapList &tl);
-int lp_wgrad_splits(const ConvGeom &g, const TapList &tl, int op);
+void lp_wgrad_plan(const ConvGeom &g, WgradPlan &p);
 // xb: x is bf16 (op 1 only)
-int lp_wgrad_launch(const float *gout, const void *x, const ConvGeom &g, const TapList &tl,
-                    int splits, float *part, hipStream_t s, int op, bool xb = false);
+void lp_wgrad_launch(const float *gout, const void *x, const ConvGeom &g, const WgradPlan &p,
+                     WgradGrid gr, float *part, hipStream_t s, bool xb = false);
 
-// A conv layer's data gradient on k_conv_lp (route ROUTE_LP / ROUTE_LP32 of conv.hip) and
+// A conv layer's data gradient on k_conv_lp (plan p: CONV_LP / CONV_LP32 of conv.hip) and
 // weight gradient (op 1: k_wgrad_lp; op 0: the k_conv_wgrad2-equivalent 64 x 64 tile) in one
-// k_lp_bwd_pair launch (e2ep_conv_bwd).  lp_bwd_pair_launch returns the weight-gradient slabs
-// written to part2 (for the split reduction), -1 if the plan has no instantiated pair.
-bool lp_bwd_pair_ok(const ConvGeom &g, int M, int op, const TapList &tl);
+// k_lp_bwd_pair launch (e2ep_conv_bwd).  lp_bwd_pair_ok says whether the two plans have an
+// instantiated pair, and sets p's tile to the pair's.
+bool lp_bwd_pair_ok(const ConvGeom &g, LpPlan &p, const WgradPlan &wp);
 // xb: x and dx are bf16 (op 1 only; dx_bytes its size in bytes)
-int lp_bwd_pair_launch(const float *w, const float *gout, const float *res, void *dx,
-                       long long dx_bytes, const ConvGeom &g, int M, int op, void *ws_dgrad,
-                       const void *x, const TapList &tl, int wsplits, float *part2,
-                       hipStream_t s, bool xb = false);
+void lp_bwd_pair_launch(const float *w, const float *gout, const float *res, void *dx,
+                        long long dx_bytes, const ConvGeom &g, int M, const LpPlan &p,
+                        void *ws_dgrad, const void *x, const WgradPlan &wp, WgradGrid gr,
+                        float *part2, hipStream_t s, bool xb = false);
 
 // Direct convolution of a 7x7 / 2 conv with 64 output channels on 16-bit operands (op 1 / 2:
 // the BEV stem in C3 / C5), conv_stem.hip: the forward (mode 0, k_conv_stem_lp) stages each

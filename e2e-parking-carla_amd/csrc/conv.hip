@@ -1561,7 +1561,7 @@ static ConvGeom make_geom(const int *d) {
   g.Cout = d[4]; g.R = d[5]; g.S = d[6]; g.P = d[7]; g.Q = d[8];
   g.sh = d[9]; g.sw = d[10]; g.ph = d[11]; g.pw = d[12]; g.dh = d[13]; g.dw = d[14];
   g.wlayout = 0;
-  g.korder = 0;  // set by korder_of() at launch
+  g.korder = 0;  // set by conv_plan()
   g.xcd = g_tune[TUNE_XCD] == 2;
   return g;
 }
@@ -1609,34 +1609,43 @@ struct GemmPlan {
   long long ncols;  // columns of the largest phase
 };
 
-// Deterministic launch plan shared by the workspace query and the launch.
 // split-K plan of the forward / data-gradient GEMMs (e2ep_conv_split_params, A/B timing)
 static int g_split_target = 1024, g_split_thresh = 512;
 static int g_wgrad_target = 1024;  // workgroups the spatial weight-gradient split aims at
+static int g_conv_precision = 0;   // GEMM operand precision: 0 fp32, 1 bf16, 2 fp16
+static int g_wgrad_kb = 16;        // k_conv_wgrad pixels per K-step (e2ep_conv_wgrad_kstep)
+static int g_gemm_variant = 0;  // 0 auto, 1 always k_conv_gemm, 2 k_conv_gemm2 wherever it
+                                // applies, 3 the same with 128-column tiles only, 4 auto with
+                                // the 1x1 forward / data gradient on the batched k_gemm, 5 the
+                                // same for maps of <= 1024 pixels only
 
+// live taps and column count of the largest stride phase, and the phase count
+static void gemm_extent(int mode, const ConvGeom &g, int &taps_max, long long &ncols, int &nph) {
+  nph = mode ? g.sh * g.sw : 1;
+  if (mode == 0) {
+    ncols = (long long)g.N * g.P * g.Q;
+    taps_max = live_taps_axis(0, 0, g.ph, g.R, g.dh, g.sh, g.H, g.P, 0) *
+               live_taps_axis(0, 0, g.pw, g.S, g.dw, g.sw, g.W, g.Q, 0);
+    return;
+  }
+  ncols = 0;
+  taps_max = 0;
+  for (int z = 0; z < nph; ++z) {
+    const int py = z / g.sw, px = z % g.sw;
+    const long long Hp = py < g.H ? (g.H - py + g.sh - 1) / g.sh : 0;
+    const long long Wp = px < g.W ? (g.W - px + g.sw - 1) / g.sw : 0;
+    ncols = std::max(ncols, (long long)g.N * Hp * Wp);
+    taps_max = std::max(taps_max, live_taps_axis(1, py, g.ph, g.R, g.dh, g.sh, g.H, g.P, (int)Hp) *
+                                      live_taps_axis(1, px, g.pw, g.S, g.dw, g.sw, g.W, g.Q, (int)Wp));
+  }
+}
+
+// Deterministic k_conv_gemm plan.
 static GemmPlan plan_gemm(int mode, const ConvGeom &g, int M) {
   GemmPlan p;
-  const int Kc = mode == 0 ? g.Cin : g.Cout;
-  const int csteps = cdiv(Kc, BK);
-  int kmax;
-  p.nph = mode ? g.sh * g.sw : 1;
-  if (mode == 0) {
-    p.ncols = (long long)g.N * g.P * g.Q;
-    kmax = live_taps_axis(0, 0, g.ph, g.R, g.dh, g.sh, g.H, g.P, 0) *
-           live_taps_axis(0, 0, g.pw, g.S, g.dw, g.sw, g.W, g.Q, 0) * csteps;
-  } else {
-    p.ncols = 0;
-    kmax = 0;
-    for (int z = 0; z < p.nph; ++z) {
-      const int py = z / g.sw, px = z % g.sw;
-      const long long Hp = py < g.H ? (g.H - py + g.sh - 1) / g.sh : 0;
-      const long long Wp = px < g.W ? (g.W - px + g.sw - 1) / g.sw : 0;
-      p.ncols = std::max(p.ncols, (long long)g.N * Hp * Wp);
-      const int taps = live_taps_axis(1, py, g.ph, g.R, g.dh, g.sh, g.H, g.P, (int)Hp) *
-                       live_taps_axis(1, px, g.pw, g.S, g.dw, g.sw, g.W, g.Q, (int)Wp);
-      kmax = std::max(kmax, taps * csteps);
-    }
-  }
+  int taps;
+  gemm_extent(mode, g, taps, p.ncols, p.nph);
+  const int kmax = taps * cdiv(mode == 0 ? g.Cin : g.Cout, BK);
   // 32-row tiles when 64-row tiles would pad M by more than 25 % (M = 24, 32, 96; measured:
   // for smaller savings the wider tile's better reuse wins, scripts/bench_conv.py)
   p.bm = 5LL * cdiv(M, 32) * 32 <= 4LL * cdiv(M, 64) * 64 ? 32 : 64;
@@ -1672,39 +1681,12 @@ static GemmPlan plan_gemm(int mode, const ConvGeom &g, int M) {
   return p;
 }
 
-static size_t gemm_workspace(const GemmPlan &p, int M) {
-  return p.splits > 1 ? (size_t)p.splits * M * p.ncols * sizeof(float) : 0;
+// split-K slabs of a forward / data-gradient plan
+static size_t splitk_bytes(int splits, int M, long long ncols) {
+  return splits > 1 ? (size_t)splits * M * ncols * sizeof(float) : 0;
 }
 
 // ---- second-generation GEMM plan (k_conv_gemm2) ------------------------------------------
-static int g_conv_precision = 0;  // GEMM operand precision: 0 fp32, 1 bf16, 2 fp16
-static int g_wgrad_kb = 16;       // k_conv_wgrad pixels per K-step (e2ep_conv_wgrad_kstep)
-static int g_gemm_variant = 0;  // 0 auto, 1 always k_conv_gemm, 2 k_conv_gemm2 wherever it
-                                // applies, 3 the same with 128-column tiles only, 4 auto with
-                                // the 1x1 forward / data gradient on the batched k_gemm, 5 the
-                                // same for maps of <= 1024 pixels only
-
-// live taps of the largest phase and the column count (as plan_gemm)
-static void gemm_extent(int mode, const ConvGeom &g, int &taps_max, long long &ncols, int &nph) {
-  nph = mode ? g.sh * g.sw : 1;
-  if (mode == 0) {
-    ncols = (long long)g.N * g.P * g.Q;
-    taps_max = live_taps_axis(0, 0, g.ph, g.R, g.dh, g.sh, g.H, g.P, 0) *
-               live_taps_axis(0, 0, g.pw, g.S, g.dw, g.sw, g.W, g.Q, 0);
-    return;
-  }
-  ncols = 0;
-  taps_max = 0;
-  for (int z = 0; z < nph; ++z) {
-    const int py = z / g.sw, px = z % g.sw;
-    const long long Hp = py < g.H ? (g.H - py + g.sh - 1) / g.sh : 0;
-    const long long Wp = px < g.W ? (g.W - px + g.sw - 1) / g.sw : 0;
-    ncols = std::max(ncols, (long long)g.N * Hp * Wp);
-    taps_max = std::max(taps_max, live_taps_axis(1, py, g.ph, g.R, g.dh, g.sh, g.H, g.P, (int)Hp) *
-                                      live_taps_axis(1, px, g.pw, g.S, g.dw, g.sw, g.W, g.Q, (int)Wp));
-  }
-}
-
 // k_conv_gemm2 applies when the tail table fits (remainder channels x taps <= V2_TAIL).
 // Automatic choice (scripts/bench_conv_variants.py, MI355X): spatial filters (R*S > 1) with
 // M >= 40 on large maps — 64 x 256 tiles when their grid fills whole rounds of 2 blocks per CU
@@ -1713,9 +1695,8 @@ static void gemm_extent(int mode, const ConvGeom &g, int &taps_max, long long &n
 // convs, small maps, split-K grids) stays on k_conv_gemm, which is faster there.
 static bool plan_gemm2(int mode, const ConvGeom &g, int M, GemmPlan &p, int &wnt) {
   if (g_gemm_variant == 1) return false;
-  int taps;
+  int taps, nph;
   long long ncols;
-  int nph;
   gemm_extent(mode, g, taps, ncols, nph);
   const int Kc = mode == 0 ? g.Cin : g.Cout;
   if ((Kc % BK) * taps > V2_TAIL || taps == 0) return false;
@@ -1796,33 +1777,169 @@ static int korder_of() {
   return g_conv_precision != 0 ? 1 : 0;
 }
 
-// The kernel family launch_gemm runs for a geometry (host only; g with korder / xcd set).
-enum ConvRoute { ROUTE_LP = 1, ROUTE_1X1 = 2, ROUTE_G2 = 3, ROUTE_LP32 = 4, ROUTE_GEMM = 5 };
-static int conv_route(int mode, const ConvGeom &g, int M) {
-  if (g_conv_precision != 0 && lp_ok(mode, g, M, g_conv_precision)) return ROUTE_LP;
-  if (conv1x1_gemm_ok(mode, g)) return ROUTE_1X1;
-  GemmPlan p2;
-  int wnt;
-  if (g.wlayout == 1 && plan_gemm2(mode, g, M, p2, wnt)) return ROUTE_G2;
-  if (g_conv_precision == 0 && g_tune[TUNE_LP32] == 2 && lp_ok(mode, g, M, 0)) return ROUTE_LP32;
-  return ROUTE_GEMM;
-}
+// the weight gradient's operands: bf16 in C3, fp32 otherwise (C5's fp16 inference included)
+static int wgrad_op() { return g_conv_precision == 1 ? 1 : 0; }
 
-// Column tiles of the forward's BatchNorm partial statistics (e2ep_conv_fwd_stats), or 0 when
-// the routed kernel does not take them (then the BN layer computes its own).
-static int fwd_stats_tiles(const ConvGeom &g0) {
-  ConvGeom g = g0;
+// ---- launch plans ------------------------------------------------------------------------
+// conv_plan() and wgrad_plan() are the only places that say which kernel family runs for a
+// geometry; the launchers, the workspace / statistics / split queries and the paired backward
+// all read their answer.  A new kernel family is a new kind, its case in the plan function and
+// its case in the launcher's switch.
+enum ConvKind { CONV_DIRECT, CONV_STEM, CONV_LP, CONV_1X1, CONV_GEMM2, CONV_LP32, CONV_GEMM };
+struct ConvPlan {
+  int kind;
+  int op;            // operand precision of the kernel: 0 fp32, 1 bf16, 2 fp16
+  GemmPlan gp;       // CONV_GEMM, CONV_GEMM2: tile, K split, phases, columns
+  int wnt;           // CONV_GEMM2: 64-column wave tiles per block (2 / 4)
+  LpPlan lp;         // CONV_LP, CONV_LP32
+  bool fold;         // K split summed inside the launch (e2ep_tune key 28 = 2), counters permitting
+  size_t workspace;  // bytes
+  int stats_tiles;   // column tiles of the forward's BatchNorm partial sums, 0 = not taken
+  int io_ok;         // E2EP_IO_* storage bits the kernel accepts
+};
+
+// The forward (mode 0) / data-gradient (mode 1) plan of g with M output rows; sets g's korder
+// and xcd.  Gates in order: the direct kernel (forward, tiny K), the BEV stem's direct kernels,
+// k_conv_lp on 16-bit operands, the batched 1x1 k_gemm, k_conv_gemm2, fp32 k_conv_lp, k_conv_gemm.
+// stem = false switches the stem kernels off: they take no statistics, no residual gradient
+// (bias in mode 1) and no bf16 storage, which a launch knows and a query cannot, so launch_gemm
+// passes !stats && !io && (mode == 0 || !bias) and the queries true.
+static ConvPlan conv_plan(int mode, ConvGeom &g, int M, bool stem = true) {
   g.korder = korder_of();
   g.xcd = g_tune[TUNE_XCD] == 2;
-  if (direct_ok(g)) return 0;
-  const int route = conv_route(0, g, g.Cout);
-  if (stem_direct_ok(0, g, g.Cout, g_conv_precision)) return 0;  // the direct stem takes no stats
-  if (route == ROUTE_LP) return lp_stats_tiles(g, g_conv_precision);
-  if (route == ROUTE_LP32) return lp_stats_tiles(g, 0);
-  if (route != ROUTE_GEMM || g_conv_precision != 0) return 0;  // fp32 k_conv_gemm only
-  const GemmPlan p = plan_gemm(0, g, g.Cout);
-  if (p.splits > 1 && g_tune[TUNE_SPLITK_FOLD] != 2) return 0;  // final values in k_conv_reduce
-  return (int)cdiv(p.ncols, p.bnt);
+  const int prec = g_conv_precision;
+  ConvPlan p{};
+  p.op = prec;
+  // a K split's values are final in the kernel's own epilogue (statistics, bf16 stores) only
+  // when the launch folds it; otherwise in the separate reduction
+  auto split_k = [&](int splits, long long ncols, int col_tile, bool stats) {
+    p.fold = splits > 1 && g_tune[TUNE_SPLITK_FOLD] == 2;
+    p.workspace = splitk_bytes(splits, M, ncols);
+    const bool final_epilogue = splits == 1 || p.fold;
+    p.stats_tiles = mode == 0 && stats && final_epilogue ? cdiv(ncols, col_tile) : 0;
+    p.io_ok = p.op != 1 ? 0 : mode == 0 ? E2EP_IO_X_BF16 : final_epilogue ? E2EP_IO_DX_BF16 : 0;
+  };
+  auto use_lp = [&](int kind, int op) {
+    p.kind = kind;
+    p.op = op;
+    p.lp = lp_plan(mode, g, M, op);
+    split_k(p.lp.splits, p.lp.ncols, 64 * p.lp.wn, true);
+  };
+  if (mode == 0 && direct_ok(g)) {
+    p.kind = CONV_DIRECT;
+    p.op = 0;
+  } else if (stem && stem_direct_ok(mode, g, M, prec)) {
+    p.kind = CONV_STEM;
+    p.workspace = stem_direct_workspace(g, mode, prec);
+  } else if (prec != 0 && lp_ok(mode, g, M, prec)) {
+    use_lp(CONV_LP, prec);
+  } else if (conv1x1_gemm_ok(mode, g)) {
+    p.kind = CONV_1X1;
+    p.workspace = conv1x1_ws(mode, g, M);
+  } else if (g.wlayout == 1 && plan_gemm2(mode, g, M, p.gp, p.wnt)) {
+    p.kind = CONV_GEMM2;
+  } else if (prec == 0 && g_tune[TUNE_LP32] == 2 && lp_ok(mode, g, M, 0)) {
+    use_lp(CONV_LP32, 0);
+  } else {
+    p.kind = CONV_GEMM;
+    p.gp = plan_gemm(mode, g, M);
+    split_k(p.gp.splits, p.gp.ncols, p.gp.bnt, prec == 0);  // statistics: fp32 k_conv_gemm only
+  }
+  return p;
+}
+
+// The workspace queries know neither the weight layout nor what a launch switches off, so they
+// answer the largest workspace of the plans those allow.  Where k_conv_lp takes the tap-major
+// geometry the answer also covers k_conv_lp's and k_conv_gemm's slabs whichever kernel runs
+// (kept from the earlier queries: callers size buffers by it).
+static size_t conv_workspace(int mode, const int *dims, int M) {
+  ConvGeom g0 = make_geom(dims), g1 = g0;  // w_layout 0 / 1
+  g1.wlayout = 1;
+  const ConvPlan p0 = conv_plan(mode, g0, M), p1 = conv_plan(mode, g1, M);
+  size_t ws = std::max(p0.workspace, p1.workspace);
+  if (p1.kind == CONV_STEM) ws = std::max(ws, conv_plan(mode, g1, M, false).workspace);
+  const int op = g_conv_precision;
+  if (p1.kind != CONV_DIRECT && (op != 0 || g_tune[TUNE_LP32] == 2) && lp_ok(mode, g1, M, op)) {
+    if (p1.kind != CONV_LP && p1.kind != CONV_LP32) {
+      const LpPlan lp = lp_plan(mode, g1, M, op);
+      ws = std::max(ws, splitk_bytes(lp.splits, M, lp.ncols));
+    }
+    if (p0.kind != CONV_GEMM) {
+      const GemmPlan gp = plan_gemm(mode, g1, M);
+      ws = std::max(ws, splitk_bytes(gp.splits, M, gp.ncols));
+    }
+  }
+  return ws;
+}
+
+// Weight-gradient plan of g for a caller's storage mask io.  Gates in order: the BEV stem's
+// direct kernel (fp32 x only), k_wgrad_lp where selected, k_wgrad_1x1, k_conv_wgrad2, k_conv_wgrad.
+static WgradPlan wgrad_plan(const ConvGeom &g, int io) {
+  WgradPlan p;
+  p.op = wgrad_op();
+  p.tl = live_taps(g);
+  p.tm = BM;
+  p.tn = WBN;
+  if (io == 0 && stem_direct_ok(2, g, g.Cout, p.op)) {
+    p.kind = WGRAD_STEM;
+    p.kstep = 0;  // its own tiles: stem_wgrad_launch
+    p.splits = stem_wgrad_splits(g);
+  } else if (lp_wgrad_selected() && lp_wgrad_ok(g, p.tl)) {
+    p.kind = WGRAD_LP;
+    lp_wgrad_plan(g, p);
+  } else if (wgrad1x1_ok(g)) {
+    p.kind = WGRAD_1X1;
+    wgrad1x1_tiles(g, p.tm, p.tn);
+    p.kstep = 8;
+    p.splits = wgrad1x1_splits_for(g, p.tm, p.tn);
+  } else {
+    // second generation when the K-step never straddles images (e2ep_tune key 9: 1 = always
+    // the first generation, for A/B timing); both on 64 x 64 tiles
+    const bool v2 = (g.P * g.Q) % W2K == 0 && g_tune[TUNE_WGRAD_GEN] != 1;
+    p.kind = v2 ? WGRAD_GEN2 : WGRAD_GEN1;
+    p.kstep = v2 ? W2K : g_wgrad_kb;
+    const long long base = (long long)cdiv(g.Cin * std::max(1, p.tl.n), WBN) * cdiv(g.Cout, BM);
+    const long long want = (g_wgrad_target + base - 1) / base;
+    const long long cap = (long long)g.N * g.P * g.Q / 256;
+    p.splits = (int)std::max(1LL, std::min({want, cap, 256LL}));
+  }
+  return p;
+}
+
+// a caller's split count as the grid: whole K-steps per slab, no empty slab
+static WgradGrid wgrad_grid(const WgradPlan &p, const ConvGeom &g, int splits) {
+  const bool groups = p.kind == WGRAD_1X1;  // k_wgrad_1x1 counts 8-pixel groups
+  const int units = g.N * g.P * g.Q / (groups ? 8 : 1), step = groups ? 1 : p.kstep;
+  WgradGrid gr;
+  gr.per = cdiv(cdiv(units, splits), step) * step;
+  gr.used = cdiv(units, gr.per);
+  return gr;
+}
+
+// ---- template dispatch: f is a generic lambda taking integral constants (conv.h IntC) ------
+// f(MODE, ACT): forward without / with ReLU, data gradient
+template <class F> static void with_mode_act(int mode, int act, F f) {
+  if (mode == 0 && act == 0) f(IntC<0>(), IntC<0>());
+  else if (mode == 0) f(IntC<0>(), IntC<1>());
+  else f(IntC<1>(), IntC<0>());
+}
+// f(BNT, BMT): the four k_conv_gemm tiles (plan_gemm yields no other)
+template <class F> static void with_gemm_tile(const GemmPlan &p, F f) {
+  if (p.bm == 64) {
+    if (p.bnt == 128) f(IntC<128>(), IntC<64>());
+    else f(IntC<64>(), IntC<64>());
+  } else {
+    if (p.bnt == 256) f(IntC<256>(), IntC<32>());
+    else f(IntC<128>(), IntC<32>());
+  }
+}
+// f(OP): operand precision 0 fp32, 1 bf16 and, for NOP = 3, 2 fp16
+template <int NOP, class F> static void with_op(int op, F f) {
+  if constexpr (NOP == 3) {
+    if (op == 2) return f(IntC<2>());
+  }
+  if (op == 1) f(IntC<1>());
+  else f(IntC<0>());
 }
 
 // io (e2ep.h E2EP_IO_*): bf16 storage of the forward input (mode 0, E2EP_IO_X_BF16) or of the
@@ -1831,130 +1948,105 @@ static int launch_gemm(int mode, int act, const float *w, const void *srcv, cons
                        void *dstv, long long dst_bytes, const ConvGeom &g0, int M, void *workspace,
                        hipStream_t s, double *stats = nullptr, int io = 0) {
   ConvGeom g = g0;
-  g.korder = korder_of();
-  g.xcd = g_tune[TUNE_XCD] == 2;
-  const int route = conv_route(mode, g, M);
-  if (stats && (mode != 0 || route == ROUTE_1X1 || route == ROUTE_G2)) {
+  const ConvPlan p = conv_plan(mode, g, M, !stats && !io && (mode == 0 || !bias));
+  if (stats && !p.stats_tiles) {
     set_error("conv: BatchNorm statistics requested from a kernel that does not take them");
     return E2EP_EINVAL;
   }
-  // the BEV stem's direct-convolution kernels (conv_stem.hip) whatever the route
-  if (!stats && !io && mode == 0 && stem_direct_ok(0, g, M, g_conv_precision))
-    return stem_direct_launch(act, g_conv_precision, w, static_cast<const float *>(srcv), bias,
-                              static_cast<float *>(dstv), dst_bytes, g, workspace, s);
-  if (!io && mode == 1 && !bias && stem_direct_ok(1, g, M, g_conv_precision))
-    return stem_dgrad_launch(g_conv_precision, w, static_cast<const float *>(srcv),
-                             static_cast<float *>(dstv), dst_bytes, g, workspace, s);
-  if (route == ROUTE_LP)
-    return lp_launch(mode, act, g_conv_precision, w, srcv, bias, dstv, dst_bytes, g, M, workspace, s,
-                     stats, io);
-  const bool sb = io && mode == 0 && io == E2EP_IO_X_BF16;
-  const bool db = io && mode == 1 && io == E2EP_IO_DX_BF16;
-  if (io && (route != ROUTE_GEMM || g_conv_precision != 1 || !(sb || db))) {
+  if (io & ~p.io_ok) {
     set_error("conv: storage mask %d not supported on this route (bf16 operands: the forward input "
-              "or the data-gradient output on k_conv_lp / k_conv_gemm)", io);
+              "or the data-gradient output on k_conv_lp / k_conv_gemm with its final epilogue)", io);
     return E2EP_EINVAL;
   }
   const float *src = static_cast<const float *>(srcv);
   float *dst = static_cast<float *>(dstv);
-  if (route == ROUTE_1X1)
-    return conv1x1_gemm(mode, act, w, src, bias, dst, dst_bytes, g, M, workspace, s);
-  if (route == ROUTE_G2) {
-    GemmPlan p2;
-    int wnt;
-    if (plan_gemm2(mode, g, M, p2, wnt)) {
-      dim3 grid(cdiv(p2.ncols, p2.bnt), cdiv(M, 64), p2.nph);
-#define G2(MD, AC, W)                                                                         \
-  do {                                                                                        \
-    if (g_conv_precision == 1)                                                                \
-      hipLaunchKernelGGL((k_conv_gemm2<MD, AC, W, 1>), grid, dim3(256), 0, s, w, src, bias, dst, \
-                         dst_bytes, g, M, 1, p2.kper);                                        \
-    else if (g_conv_precision == 2)                                                           \
-      hipLaunchKernelGGL((k_conv_gemm2<MD, AC, W, 2>), grid, dim3(256), 0, s, w, src, bias, dst, \
-                         dst_bytes, g, M, 1, p2.kper);                                        \
-    else                                                                                      \
-      hipLaunchKernelGGL((k_conv_gemm2<MD, AC, W, 0>), grid, dim3(256), 0, s, w, src, bias, dst, \
-                         dst_bytes, g, M, 1, p2.kper);                                        \
-  } while (0)
-      if (mode == 0 && act == 0) { if (wnt == 4) G2(0, 0, 4); else G2(0, 0, 2); }
-      else if (mode == 0) { if (wnt == 4) G2(0, 1, 4); else G2(0, 1, 2); }
-      else { if (wnt == 4) G2(1, 0, 4); else G2(1, 0, 2); }
-#undef G2
+  const GemmPlan &gp = p.gp;
+  switch (p.kind) {
+    case CONV_DIRECT:
+      hipLaunchKernelGGL(k_conv_direct, dim3(cdiv((long long)g.N * g.P * g.Q, 256)), dim3(256), 0, s,
+                         src, w, bias, g, act, dst);
+      return 0;
+    case CONV_STEM:
+      return mode == 0 ? stem_direct_launch(act, p.op, w, src, bias, dst, dst_bytes, g, workspace, s)
+                       : stem_dgrad_launch(p.op, w, src, dst, dst_bytes, g, workspace, s);
+    case CONV_LP:
+    case CONV_LP32:
+      return lp_launch(mode, act, p.op, w, srcv, bias, dstv, dst_bytes, g, M, p.lp, workspace, s,
+                       stats, io);
+    case CONV_1X1:
+      return conv1x1_gemm(mode, act, w, src, bias, dst, dst_bytes, g, M, workspace, s);
+    case CONV_GEMM2: {
+      const dim3 grid(cdiv(gp.ncols, gp.bnt), cdiv(M, 64), gp.nph);
+      with_mode_act(mode, act, [&](auto md, auto ac) {
+        auto wide = [&](auto wv) {
+          with_op<3>(p.op, [&](auto opc) {
+            hipLaunchKernelGGL((k_conv_gemm2<decltype(md)::value, decltype(ac)::value,
+                                             decltype(wv)::value, decltype(opc)::value>),
+                               grid, dim3(256), 0, s, w, src, bias, dst, dst_bytes, g, M, 1, gp.kper);
+          });
+        };
+        if (p.wnt == 4) wide(IntC<4>());
+        else wide(IntC<2>());
+      });
       return 0;
     }
+    default:
+      break;  // CONV_GEMM
   }
-  if (route == ROUTE_LP32)
-    return lp_launch(mode, act, 0, w, src, bias, dst, dst_bytes, g, M, workspace, s, stats);
-  const GemmPlan p = plan_gemm(mode, g, M);
-  dim3 grid(cdiv(p.ncols, p.bnt), cdiv(M, p.bm), p.nph * p.splits);
+  const dim3 grid(cdiv(gp.ncols, gp.bnt), cdiv(M, gp.bm), gp.nph * gp.splits);
   float *part = nullptr;
   unsigned int *cnt = nullptr;
-  if (p.splits > 1) {
+  if (gp.splits > 1) {
     if (!workspace) {
       set_error("conv: split-K plan needs a workspace (query the *_workspace entry point)");
       return E2EP_EINVAL;
     }
     part = static_cast<float *>(workspace);
     // in-launch fold (e2ep_tune key 28 = 2): one arrival counter per output tile
-    if (g_tune[TUNE_SPLITK_FOLD] == 2) cnt = handoff_slots((int)grid.x * (int)grid.y, s);
+    if (p.fold) cnt = handoff_slots((int)grid.x * (int)grid.y, s);
   }
-  if (stats && p.splits > 1 && !cnt) {
-    set_error("conv: BatchNorm statistics need the in-launch split-K fold (e2ep_tune key 28 = 2)");
-    return E2EP_EINVAL;
-  }
-  if (db && p.splits > 1 && !cnt) {
-    set_error("conv: a bf16 data gradient needs the in-launch split-K fold (e2ep_tune key 28 = 2)");
+  const bool sb = io == E2EP_IO_X_BF16, db = io == E2EP_IO_DX_BF16;
+  if ((stats || db) && gp.splits > 1 && !cnt) {
+    set_error("conv: BatchNorm statistics and a bf16 data gradient need the in-launch split-K fold "
+              "(e2ep_tune key 28 = 2) and its arrival counters");
     return E2EP_EINVAL;
   }
   const bool av = mode == 0 && g.wlayout == 1 && (g.Cin & 3) == 0;
-#define GEMM_LAUNCH1(MD, AC, BT, BMT, V)                                                          \
-  do {                                                                                             \
-    if (g_conv_precision == 1 && MD == 0 && sb)                                                    \
-      hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 1, false, bf16_t, float>), grid, dim3(256), 0, s, \
-                         w, static_cast<const bf16_t *>(srcv), bias, dst, dst_bytes, g, M, p.splits, \
-                         p.kper, part, cnt, nullptr);                                              \
-    else if (g_conv_precision == 1 && MD == 1 && db)                                               \
-      hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 1, false, float, bf16_t>), grid, dim3(256), 0, s, \
-                         w, src, bias, static_cast<bf16_t *>(dstv), dst_bytes, g, M, p.splits,     \
-                         p.kper, part, cnt, nullptr);                                              \
-    else if (g_conv_precision == 1)                                                                \
-      hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 1>), grid, dim3(256), 0, s, w, src, bias, \
-                         dst, dst_bytes, g, M, p.splits, p.kper, part, cnt, nullptr);             \
-    else if (g_conv_precision == 2)                                                                \
-      hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 2>), grid, dim3(256), 0, s, w, src, bias, \
-                         dst, dst_bytes, g, M, p.splits, p.kper, part, cnt, nullptr);             \
-    else if (MD == 0 && stats)                                                                     \
-      hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 0, true>), grid, dim3(256), 0, s, w, src, \
-                         bias, dst, dst_bytes, g, M, p.splits, p.kper, part, cnt, stats);         \
-    else                                                                                           \
-      hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 0>), grid, dim3(256), 0, s, w, src, bias, \
-                         dst, dst_bytes, g, M, p.splits, p.kper, part, cnt, nullptr);             \
-  } while (0)
-#define GEMM_LAUNCH(MD, AC, BT, BMT)                                  \
-  do {                                                                \
-    if (MD == 0 && BMT == 64 && av) GEMM_LAUNCH1(MD, AC, BT, BMT, MD == 0 && BMT == 64); \
-    else GEMM_LAUNCH1(MD, AC, BT, BMT, false);                        \
-  } while (0)
-#define GEMM_TILES(MD, AC)                                             \
-  do {                                                                 \
-    if (p.bm == 64) {                                                  \
-      if (p.bnt == 128) GEMM_LAUNCH(MD, AC, 128, 64);                  \
-      else GEMM_LAUNCH(MD, AC, 64, 64);                                \
-    } else {                                                           \
-      if (p.bnt == 256) GEMM_LAUNCH(MD, AC, 256, 32);                  \
-      else GEMM_LAUNCH(MD, AC, 128, 32);                               \
-    }                                                                  \
-  } while (0)
-  if (mode == 0 && act == 0) GEMM_TILES(0, 0);
-  else if (mode == 0) GEMM_TILES(0, 1);
-  else GEMM_TILES(1, 0);
-#undef GEMM_TILES
-#undef GEMM_LAUNCH
-#undef GEMM_LAUNCH1
-  if (p.splits > 1 && !cnt) {
+  with_mode_act(mode, act, [&](auto md, auto ac) {
+    with_gemm_tile(gp, [&](auto bt, auto bmt) {
+      constexpr int MD = decltype(md)::value, AC = decltype(ac)::value;
+      constexpr int BT = decltype(bt)::value, BMT = decltype(bmt)::value;
+      auto launch = [&](auto vec) {  // vec: float4 weight loads (forward, 64-row tiles)
+        constexpr bool V = decltype(vec)::value;
+        if (p.op == 1 && MD == 0 && sb)
+          hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 1, false, bf16_t, float>), grid, dim3(256), 0, s,
+                             w, static_cast<const bf16_t *>(srcv), bias, dst, dst_bytes, g, M, gp.splits,
+                             gp.kper, part, cnt, nullptr);
+        else if (p.op == 1 && MD == 1 && db)
+          hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 1, false, float, bf16_t>), grid, dim3(256), 0, s,
+                             w, src, bias, static_cast<bf16_t *>(dstv), dst_bytes, g, M, gp.splits,
+                             gp.kper, part, cnt, nullptr);
+        else if (p.op == 1)
+          hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 1>), grid, dim3(256), 0, s, w, src, bias,
+                             dst, dst_bytes, g, M, gp.splits, gp.kper, part, cnt, nullptr);
+        else if (p.op == 2)
+          hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 2>), grid, dim3(256), 0, s, w, src, bias,
+                             dst, dst_bytes, g, M, gp.splits, gp.kper, part, cnt, nullptr);
+        else if (MD == 0 && stats)
+          hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 0, true>), grid, dim3(256), 0, s, w, src,
+                             bias, dst, dst_bytes, g, M, gp.splits, gp.kper, part, cnt, stats);
+        else
+          hipLaunchKernelGGL((k_conv_gemm<MD, AC, BT, BMT, V, 0>), grid, dim3(256), 0, s, w, src, bias,
+                             dst, dst_bytes, g, M, gp.splits, gp.kper, part, cnt, nullptr);
+      };
+      if (MD == 0 && BMT == 64 && av) launch(std::integral_constant<bool, MD == 0 && BMT == 64>());
+      else launch(std::false_type());
+    });
+  });
+  if (gp.splits > 1 && !cnt) {
     const int HW = mode == 0 ? g.P * g.Q : g.H * g.W;
-    hipLaunchKernelGGL(k_conv_reduce, dim3(cdiv(p.ncols, 256), M), dim3(256), 0, s,
-                       static_cast<const float *>(workspace), p.splits, M, HW, (int)p.ncols,
+    hipLaunchKernelGGL(k_conv_reduce, dim3(cdiv(gp.ncols, 256), M), dim3(256), 0, s,
+                       static_cast<const float *>(workspace), gp.splits, M, HW, (int)gp.ncols,
                        mode == 0 ? bias : nullptr, act, mode == 1 ? bias : nullptr, dst);
   }
   return 0;
@@ -1962,51 +2054,10 @@ static int launch_gemm(int mode, int act, const float *w, const void *srcv, cons
 
 extern "C" {
 
-// (sized for the k_conv_gemm plan; the k_conv_gemm2 path needs none, so a caller may pass a
-// workspace sized by these queries whichever kernel runs)
-static size_t conv_fwd_workspace(const int *dims);
-size_t e2ep_conv_fwd_workspace(const int *dims) {
-  ConvGeom g = make_geom(dims);
-  g.wlayout = 1;  // w_layout unknown here: cover the direct stem's weight image
-  const size_t ws = conv_fwd_workspace(dims);
-  return stem_direct_ok(0, g, g.Cout, g_conv_precision)
-             ? std::max(ws, stem_direct_workspace(g, 0, g_conv_precision)) : ws;
-}
-static size_t conv_fwd_workspace(const int *dims) {
-  ConvGeom g = make_geom(dims);
-  if (direct_ok(g)) return 0;
-  if (g_conv_precision != 0 || g_tune[TUNE_LP32] == 2) {  // w_layout unknown here: cover all
-    g.wlayout = 1;
-    if (lp_ok(0, g, g.Cout, g_conv_precision)) {
-      size_t ws = std::max(lp_workspace(0, g, g.Cout, g_conv_precision),
-                           gemm_workspace(plan_gemm(0, g, g.Cout), g.Cout));
-      return ws;
-    }
-  }
-  if (conv1x1_gemm_ok(0, g)) return conv1x1_ws(0, g, g.Cout);
-  return gemm_workspace(plan_gemm(0, g, g.Cout), g.Cout);
-}
+size_t e2ep_conv_fwd_workspace(const int *dims) { return conv_workspace(0, dims, dims[4]); }
 
-static size_t conv_dgrad_workspace(const int *dims, int m_channels);
 size_t e2ep_conv_dgrad_workspace(const int *dims, int m_channels) {
-  ConvGeom g = make_geom(dims);
-  g.wlayout = 1;
-  const size_t ws = conv_dgrad_workspace(dims, m_channels);
-  return stem_direct_ok(1, g, m_channels, g_conv_precision)
-             ? std::max(ws, stem_direct_workspace(g, 1, g_conv_precision)) : ws;
-}
-static size_t conv_dgrad_workspace(const int *dims, int m_channels) {
-  ConvGeom g = make_geom(dims);
-  if (g_conv_precision != 0 || g_tune[TUNE_LP32] == 2) {
-    g.wlayout = 1;
-    if (lp_ok(1, g, m_channels, g_conv_precision)) {
-      size_t ws = std::max(lp_workspace(1, g, m_channels, g_conv_precision),
-                           gemm_workspace(plan_gemm(1, g, m_channels), m_channels));
-      return ws;
-    }
-  }
-  if (conv1x1_gemm_ok(1, g)) return conv1x1_ws(1, g, m_channels);
-  return gemm_workspace(plan_gemm(1, g, m_channels), m_channels);
+  return conv_workspace(1, dims, m_channels);
 }
 
 int e2ep_conv_precision(int precision) {
@@ -2038,7 +2089,7 @@ int e2ep_conv_fwd_stats_tiles(const int *dims, int w_layout) {
   ConvGeom g = make_geom(dims);
   g.wlayout = w_layout;
   if (!geom_ok(g) || (w_layout != 0 && w_layout != 1)) return 0;
-  return fwd_stats_tiles(g);
+  return conv_plan(0, g, g.Cout).stats_tiles;
 }
 
 int e2ep_conv_fwd(const void *x, const float *w, const float *bias, const int *dims, int act,
@@ -2063,7 +2114,7 @@ int e2ep_conv_fwd_stats(const void *x, const float *w, const float *bias, const 
   E2EP_REQUIRE(geom_ok(g), E2EP_EINVAL, "e2ep_conv_fwd: bad geometry");
   E2EP_REQUIRE(act == 0 || act == 1, E2EP_EINVAL, "e2ep_conv_fwd: act must be 0 (none) or 1 (relu)");
   if (stats) {  // BatchNorm partials [Cout][tiles][2] from the epilogue (bnstats.h)
-    const int tiles = fwd_stats_tiles(g);
+    const int tiles = conv_plan(0, g, g.Cout).stats_tiles;  // what e2ep_conv_fwd_stats_tiles answers
     E2EP_REQUIRE(tiles > 0, E2EP_EINVAL,
                  "e2ep_conv_fwd_stats: this geometry's kernel takes no statistics "
                  "(e2ep_conv_fwd_stats_tiles returned 0)");
@@ -2073,12 +2124,6 @@ int e2ep_conv_fwd_stats(const void *x, const float *w, const float *bias, const 
   }
   E2EP_REQUIRE(io == 0 || io == E2EP_IO_X_BF16, E2EP_EINVAL,
                "e2ep_conv_fwd: storage mask %d not supported (0 or X bf16)", io);
-  if (direct_ok(g)) {
-    E2EP_REQUIRE(io == 0, E2EP_EINVAL, "e2ep_conv_fwd: the direct kernel reads fp32 x only");
-    hipLaunchKernelGGL(k_conv_direct, dim3(cdiv((long long)g.N * g.P * g.Q, 256)), dim3(256), 0,
-                       as_stream(stream), static_cast<const float *>(x), w, bias, g, act, y);
-    return launch_status("e2ep_conv_fwd");
-  }
   const int rc = launch_gemm(0, act, w, x, bias, y, 4LL * g.N * g.Cout * g.P * g.Q, g, g.Cout,
                              workspace, as_stream(stream), stats, io);
   if (rc) return rc;
@@ -2116,22 +2161,9 @@ int e2ep_conv_dgrad(const float *gout, const float *w, const int *dims, int m_ch
 }
 
 int e2ep_conv_wgrad_splits(const int *dims) {
-  ConvGeom g = make_geom(dims);
-  if (stem_direct_ok(2, g, g.Cout, g_conv_precision == 1 ? 1 : 0)) return stem_wgrad_splits(g);
-  if (lp_wgrad_selected()) {  // k_wgrad_lp (conv_lp.hip): C3 bf16, or fp32 when selected
-    const TapList tl = live_taps(g);
-    if (lp_wgrad_ok(g, tl)) return lp_wgrad_splits(g, tl, g_conv_precision == 1 ? 1 : 0);
-  }
-  if (wgrad1x1_ok(g)) return wgrad1x1_splits(g);
-  const int nl = std::max(1, live_taps(g).n);
-  const long long base = (long long)cdiv(g.Cin * nl, WBN) * cdiv(g.Cout, BM);
-  const long long pix = (long long)g.N * g.P * g.Q;
-  long long want = (g_wgrad_target + base - 1) / base;
-  long long cap = pix / 256;
-  long long s = want < cap ? want : cap;
-  if (s < 1) s = 1;
-  if (s > 256) s = 256;
-  return (int)s;
+  // no io argument: the answer is the io = 0 plan's.  A bf16 x can move the launch to another
+  // kernel, which then runs with this count as its cap (every kernel takes any splits >= 1).
+  return wgrad_plan(make_geom(dims), 0).splits;
 }
 
 size_t e2ep_conv_wgrad_workspace(const int *dims, int splits) {
@@ -2139,10 +2171,42 @@ size_t e2ep_conv_wgrad_workspace(const int *dims, int splits) {
   return (size_t)splits * g.Cout * g.Cin * g.R * g.S * sizeof(float);
 }
 
+// The weight-gradient GEMM of plan p (not the stem's) into the slabs of `part`.
+static void launch_wgrad(const WgradPlan &p, WgradGrid gr, const float *gout, const void *xv,
+                         const ConvGeom &g, float *part, hipStream_t s, bool xb) {
+  const float *x = static_cast<const float *>(xv);
+  const TapList &tl = p.tl;
+  if (tl.n <= 0) return;  // no live tap: the reduction writes the zeros
+  const dim3 grid(cdiv(g.Cin * tl.n, p.tn), cdiv(g.Cout, p.tm), gr.used);
+  if (p.kind == WGRAD_LP) {
+    lp_wgrad_launch(gout, xv, g, p, gr, part, s, xb);
+  } else if (p.kind == WGRAD_1X1) {
+    const dim3 grid1(cdiv(g.Cout, p.tm) * cdiv(g.Cin, p.tn), gr.used);
+    with_tile2x2(p.tm == 64, p.tn == 64, [&](auto ti, auto tj) {
+      with_op<2>(p.op, [&](auto opc) {
+        hipLaunchKernelGGL((k_wgrad_1x1<decltype(ti)::value, decltype(tj)::value, decltype(opc)::value>),
+                           grid1, dim3(256), 0, s, gout, x, part, g, gr.used, gr.per);
+      });
+    });
+  } else if (p.kind == WGRAD_GEN2) {
+    with_op<2>(p.op, [&](auto opc) {
+      hipLaunchKernelGGL((k_conv_wgrad2<decltype(opc)::value>), grid, dim3(256), 0, s, gout, x, part,
+                         g, gr.per, tl);
+    });
+  } else {  // bf16 operands in C3 (fp32 accumulate / gradient); pixel K-step 16 or 32
+    with_op<2>(p.op, [&](auto opc) {
+      constexpr int OP = decltype(opc)::value;
+      if (p.kstep == 32)
+        hipLaunchKernelGGL((k_conv_wgrad<OP, 32>), grid, dim3(256), 0, s, gout, x, part, g, gr.per, tl);
+      else
+        hipLaunchKernelGGL((k_conv_wgrad<OP, 16>), grid, dim3(256), 0, s, gout, x, part, g, gr.per, tl);
+    });
+  }
+}
+
 int e2ep_conv_wgrad(const float *gout, const void *xv, const int *dims, int splits,
                     void *workspace, size_t workspace_bytes, float *dw, int accumulate,
                     void *stream, int io) {
-  const float *x = static_cast<const float *>(xv);
   ConvGeom g = make_geom(dims);
   E2EP_REQUIRE(geom_ok(g) && splits > 0, E2EP_EINVAL, "e2ep_conv_wgrad: bad geometry");
   // the kernels write at most `splits` slabs of Cout * Cin * R * S floats
@@ -2151,132 +2215,57 @@ int e2ep_conv_wgrad(const float *gout, const void *xv, const int *dims, int spli
                workspace_bytes, e2ep_conv_wgrad_workspace(dims, splits), splits);
   E2EP_REQUIRE(io == 0 || io == E2EP_IO_X_BF16, E2EP_EINVAL,
                "e2ep_conv_wgrad: storage mask %d not supported (0 or X bf16)", io);
-  // the weight gradient's operands: bf16 in C3, fp32 otherwise (C5's fp16 mode included)
-  if (io == 0 && stem_direct_ok(2, g, g.Cout, g_conv_precision == 1 ? 1 : 0)) {
-    hipStream_t s = as_stream(stream);
-    float *part = static_cast<float *>(workspace);
-    const int used = stem_wgrad_launch(gout, x, g, splits, part, s, g_conv_precision == 1 ? 1 : 0);
-    E2EP_REQUIRE(used > 0, E2EP_EINVAL, "e2ep_conv_wgrad: direct stem weight gradient refused");
-    reduce_splits(part, used, g.Cout * g.Cin * g.R * g.S, dw, accumulate, g.R * g.S, live_taps(g).mask, s);
-    return launch_status("e2ep_conv_wgrad");
-  }
-  if (lp_wgrad_selected()) {
-    const TapList tl = live_taps(g);
-    if (lp_wgrad_ok(g, tl)) {
-      E2EP_REQUIRE(io == 0 || g_conv_precision == 1, E2EP_EINVAL,
-                   "e2ep_conv_wgrad: a bf16 x needs the bf16-operand weight gradient");
-      hipStream_t s = as_stream(stream);
-      float *part = static_cast<float *>(workspace);
-      const int used = lp_wgrad_launch(gout, xv, g, tl, splits, part, s, g_conv_precision == 1 ? 1 : 0,
-                                       io != 0);
-      reduce_splits(part, used, g.Cout * g.Cin * g.R * g.S, dw, accumulate, g.R * g.S, tl.mask, s);
-      return launch_status("e2ep_conv_wgrad");
-    }
-  }
-  E2EP_REQUIRE(io == 0, E2EP_EINVAL,
+  const WgradPlan p = wgrad_plan(g, io);
+  E2EP_REQUIRE(io == 0 || (p.kind == WGRAD_LP && p.op == 1), E2EP_EINVAL,
                "e2ep_conv_wgrad: a bf16 x runs on the bf16-operand weight gradient (k_wgrad_lp) only");
-  if (wgrad1x1_ok(g)) {
-    const int groups = g.N * g.P * g.Q / 8;
-    const int gps = cdiv(groups, splits);
-    const int used = cdiv(groups, gps);
-    hipStream_t s = as_stream(stream);
-    float *part = static_cast<float *>(workspace);
-    int to, tc;
-    wgrad1x1_tiles(g, to, tc);
-    const dim3 grid(cdiv(g.Cout, to) * cdiv(g.Cin, tc), used);
-#define W1_LAUNCH(TI, TJ)                                                                      \
-  do {                                                                                         \
-    if (g_conv_precision == 1)                                                                 \
-      hipLaunchKernelGGL((k_wgrad_1x1<TI, TJ, 1>), grid, dim3(256), 0, s, gout, x, part, g, used, \
-                         gps);                                                                 \
-    else                                                                                       \
-      hipLaunchKernelGGL((k_wgrad_1x1<TI, TJ, 0>), grid, dim3(256), 0, s, gout, x, part, g, used, \
-                         gps);                                                                 \
-  } while (0)
-    if (to == 64 && tc == 64) W1_LAUNCH(2, 2);
-    else if (to == 64) W1_LAUNCH(2, 1);
-    else if (tc == 64) W1_LAUNCH(1, 2);
-    else W1_LAUNCH(1, 1);
-#undef W1_LAUNCH
-    const int n = g.Cout * g.Cin;
-    reduce_splits(part, used, n, dw, accumulate, 1, 1ULL, s);
-    return launch_status("e2ep_conv_wgrad");
-  }
-  const int Ptot = g.N * g.P * g.Q;
-  // second generation when the K-step never straddles images (e2ep_tune key 9: 1 = always
-  // the first generation, for A/B timing)
-  const bool v2 = (g.P * g.Q) % W2K == 0 && g_tune[TUNE_WGRAD_GEN] != 1;
-  const int kb = v2 ? W2K : g_wgrad_kb;
-  int per = (Ptot + splits - 1) / splits;
-  per = (per + kb - 1) / kb * kb;
-  const int used = (Ptot + per - 1) / per;
-  const TapList tl = live_taps(g);
   hipStream_t s = as_stream(stream);
   float *part = static_cast<float *>(workspace);
-  if (tl.n > 0 && v2) {
-    dim3 grid(cdiv(g.Cin * tl.n, 64), cdiv(g.Cout, 64), used);
-    if (g_conv_precision == 1)
-      hipLaunchKernelGGL((k_conv_wgrad2<1>), grid, dim3(256), 0, s, gout, x, part, g, per, tl);
-    else
-      hipLaunchKernelGGL((k_conv_wgrad2<0>), grid, dim3(256), 0, s, gout, x, part, g, per, tl);
-  } else if (tl.n > 0) {
-    dim3 grid(cdiv(g.Cin * tl.n, WBN), cdiv(g.Cout, BM), used);
-#define WG_LAUNCH(OPV, KBV) \
-  hipLaunchKernelGGL((k_conv_wgrad<OPV, KBV>), grid, dim3(256), 0, s, gout, x, part, g, per, tl)
-    // bf16 operands in C3 (fp32 accumulate / gradient); pixel K-step 16 or 32
-    if (g_conv_precision == 1) {
-      if (kb == 32) WG_LAUNCH(1, 32); else WG_LAUNCH(1, 16);
-    } else {
-      if (kb == 32) WG_LAUNCH(0, 32); else WG_LAUNCH(0, 16);
-    }
-#undef WG_LAUNCH
+  int used;
+  if (p.kind == WGRAD_STEM) {
+    used = stem_wgrad_launch(gout, static_cast<const float *>(xv), g, splits, part, s, p.op);
+    E2EP_REQUIRE(used > 0, E2EP_EINVAL, "e2ep_conv_wgrad: direct stem weight gradient refused");
+  } else {
+    const WgradGrid gr = wgrad_grid(p, g, splits);
+    launch_wgrad(p, gr, gout, xv, g, part, s, io != 0);
+    used = gr.used;
   }
-  const int n = g.Cout * g.Cin * g.R * g.S;
-  reduce_splits(part, used, n, dw, accumulate, g.R * g.S, tl.mask, s);
+  reduce_splits(part, used, g.Cout * g.Cin * g.R * g.S, dw, accumulate, g.R * g.S, p.tl.mask, s);
   return launch_status("e2ep_conv_wgrad");
 }
 
-// The paired backward of e2ep_conv_bwd, where the two-launch path's kernels have a paired
-// instantiation: PAIR_GEMM = fp32 k_conv_gemm data gradient (one split or folded splits) with
-// k_conv_wgrad2 (k_conv_bwd_pair); PAIR_LP = k_conv_lp data gradient (fp32 where TUNE_LP32
-// routes it, bf16 in C3) with the k_wgrad_lp / k_conv_wgrad2 weight gradient (k_lp_bwd_pair).
+// The paired backward of e2ep_conv_bwd, where the two-launch path's plans have a paired
+// instantiation: PAIR_GEMM / PAIR_GEMM1X1 = fp32 k_conv_gemm data gradient (one split or folded
+// splits) with k_conv_wgrad2 (k_conv_bwd_pair) / k_wgrad_1x1 (k_conv_bwd_pair1x1); PAIR_LP =
+// k_conv_lp data gradient (fp32 where TUNE_LP32 routes it, bf16 in C3) with the k_conv_wgrad2 /
+// k_wgrad_lp weight gradient (k_lp_bwd_pair).  dp, wp: the two plans (dp.lp with the pair's tile).
 enum PairKind { PAIR_NONE = 0, PAIR_GEMM = 1, PAIR_LP = 2, PAIR_GEMM1X1 = 3 };
-static int conv_bwd_pair_plan(ConvGeom &g, int m_channels, GemmPlan &p, TapList &tl) {
+static int conv_bwd_pair_plan(ConvGeom &g, int m_channels, ConvPlan &dp, WgradPlan &wp) {
   g.wlayout = 1;
-  g.korder = korder_of();
-  g.xcd = g_tune[TUNE_XCD] == 2;
   if (!geom_ok(g) || m_channels <= 0 || m_channels > g.Cin) return PAIR_NONE;
-  tl = live_taps(g);
-  if (tl.n <= 0) return PAIR_NONE;
-  // the BEV stem on the direct-convolution kernels (conv_stem.hip) runs its two gradients as
-  // separate launches (both faster than the paired implicit GEMMs)
-  if (stem_direct_ok(1, g, m_channels, g_conv_precision) || stem_direct_ok(2, g, g.Cout, g_conv_precision))
-    return PAIR_NONE;
-  // the weight-gradient kernel e2ep_conv_wgrad would run
-  const bool wg_lp = lp_wgrad_selected() && lp_wgrad_ok(g, tl);
-  const bool wg_2 = !wg_lp && !wgrad1x1_ok(g) && (g.P * g.Q) % W2K == 0 &&
-                    g_tune[TUNE_WGRAD_GEN] != 1;
-  const int route = conv_route(1, g, m_channels);
-  const bool wg_1x1 = !wg_lp && wgrad1x1_ok(g);
-  if (g_conv_precision == 0 && route == ROUTE_GEMM && (wg_2 || wg_1x1)) {
-    p = plan_gemm(1, g, m_channels);
-    if (p.splits > 1 && g_tune[TUNE_SPLITK_FOLD] != 2) return PAIR_NONE;
-    const bool tile_ok = (p.bm == 64 && (p.bnt == 64 || p.bnt == 128)) ||
-                         (p.bm == 32 && (p.bnt == 128 || p.bnt == 256));
-    return tile_ok ? (wg_1x1 ? PAIR_GEMM1X1 : PAIR_GEMM) : PAIR_NONE;
+  wp = wgrad_plan(g, 0);
+  if (wp.tl.n <= 0) return PAIR_NONE;
+  dp = conv_plan(1, g, m_channels);
+  // The BEV stem on the direct-convolution kernels (conv_stem.hip) runs its two gradients as
+  // separate launches (both faster than the paired implicit GEMMs).  (The stem gate once got the
+  // raw precision here and wgrad_op() elsewhere: they differ in fp16 mode only, where no branch
+  // below pairs.)
+  if (dp.kind == CONV_STEM || wp.kind == WGRAD_STEM) return PAIR_NONE;
+  const int prec = g_conv_precision;
+  if (prec == 0 && dp.kind == CONV_GEMM && (wp.kind == WGRAD_GEN2 || wp.kind == WGRAD_1X1)) {
+    if (dp.gp.splits > 1 && !dp.fold) return PAIR_NONE;
+    return wp.kind == WGRAD_1X1 ? PAIR_GEMM1X1 : PAIR_GEMM;
   }
-  if (g_conv_precision == 0 && route == ROUTE_LP32 && wg_2)
-    return lp_bwd_pair_ok(g, m_channels, 0, tl) ? PAIR_LP : PAIR_NONE;
-  if (g_conv_precision == 1 && route == ROUTE_LP && wg_lp)
-    return lp_bwd_pair_ok(g, m_channels, 1, tl) ? PAIR_LP : PAIR_NONE;
+  if ((prec == 0 && dp.kind == CONV_LP32 && wp.kind == WGRAD_GEN2) ||
+      (prec == 1 && dp.kind == CONV_LP && wp.kind == WGRAD_LP))
+    return lp_bwd_pair_ok(g, dp.lp, wp) ? PAIR_LP : PAIR_NONE;
   return PAIR_NONE;
 }
 
 int e2ep_conv_bwd_pair_ok(const int *dims, int m_channels) {
   ConvGeom g = make_geom(dims);
-  GemmPlan p;
-  TapList tl;
-  return conv_bwd_pair_plan(g, m_channels, p, tl) != PAIR_NONE ? 1 : 0;
+  ConvPlan dp;
+  WgradPlan wp;
+  return conv_bwd_pair_plan(g, m_channels, dp, wp) != PAIR_NONE ? 1 : 0;
 }
 
 int e2ep_conv_bwd(const float *gout, const void *xv, const float *w, const int *dims,
@@ -2286,9 +2275,9 @@ int e2ep_conv_bwd(const float *gout, const void *xv, const float *w, const int *
   const float *x = static_cast<const float *>(xv);
   float *dx = static_cast<float *>(dxv);
   ConvGeom g = make_geom(dims);
-  GemmPlan p;
-  TapList tl;
-  const int kind = conv_bwd_pair_plan(g, m_channels, p, tl);
+  ConvPlan dp;
+  WgradPlan wp;
+  const int kind = conv_bwd_pair_plan(g, m_channels, dp, wp);
   E2EP_REQUIRE(kind != PAIR_NONE, E2EP_EINVAL,
                "e2ep_conv_bwd: this geometry / setting has no paired backward "
                "(e2ep_conv_bwd_pair_ok returned 0)");
@@ -2308,78 +2297,44 @@ int e2ep_conv_bwd(const float *gout, const void *xv, const float *w, const int *
   const int M = m_channels;
   const long long dx_bytes = (xb ? 2LL : 4LL) * g.N * M * g.H * g.W;
   float *part2 = static_cast<float *>(ws_wgrad);
-  int used;
+  const WgradGrid gr = wgrad_grid(wp, g, wsplits);
+  const TapList &tl = wp.tl;
   if (kind == PAIR_LP) {
-    used = lp_bwd_pair_launch(w, gout, res, dxv, dx_bytes, g, M, g_conv_precision == 1 ? 1 : 0,
-                              ws_dgrad, xv, tl, wsplits, part2, s, xb);
-    E2EP_REQUIRE(used > 0, E2EP_EINVAL, "e2ep_conv_bwd: no paired k_conv_lp plan");
-    reduce_splits(part2, used, g.Cout * g.Cin * g.R * g.S, dw, 0, g.R * g.S, tl.mask, s);
-    return launch_status("e2ep_conv_bwd");
-  }
-  // k_conv_gemm data gradient: launch_gemm's grid and fold counters
-  const dim3 g1(cdiv(p.ncols, p.bnt), cdiv(M, p.bm), p.nph * p.splits);
-  float *part1 = p.splits > 1 ? static_cast<float *>(ws_dgrad) : nullptr;
-  unsigned int *cnt = p.splits > 1 ? handoff_slots((int)g1.x * (int)g1.y, s) : nullptr;
-  if (kind == PAIR_GEMM1X1) {
-    // e2ep_conv_wgrad's k_wgrad_1x1 plan
-    const int groups = g.N * g.P * g.Q / 8;
-    const int gps = cdiv(groups, wsplits);
-    used = cdiv(groups, gps);
-    int to, tc;
-    wgrad1x1_tiles(g, to, tc);
-    const int nt2 = cdiv(g.Cout, to) * cdiv(g.Cin, tc);
-    const dim3 grid(g1.x * g1.y * g1.z + nt2 * used);
-    const int wfirst = g_tune[TUNE_PAIR1X1_ORDER] == 2 ? 1 : 0;
-#define E2EP_PAIR1(BNTV, BMTV, TIV, TJV)                                                          \
-  hipLaunchKernelGGL((k_conv_bwd_pair1x1<BNTV, BMTV, TIV, TJV>), grid, dim3(256), 0, s, w, gout,  \
-                     res, dx, dx_bytes, g, M, p.splits, p.kper, part1, cnt, (int)g1.x, (int)g1.y,  \
-                     (int)g1.z, x, part2, used, gps, nt2, wfirst)
-#define E2EP_PAIR1_W(BNTV, BMTV)                                          \
-  do {                                                                    \
-    if (to == 64 && tc == 64) E2EP_PAIR1(BNTV, BMTV, 2, 2);               \
-    else if (to == 64) E2EP_PAIR1(BNTV, BMTV, 2, 1);                      \
-    else if (tc == 64) E2EP_PAIR1(BNTV, BMTV, 1, 2);                      \
-    else E2EP_PAIR1(BNTV, BMTV, 1, 1);                                    \
-  } while (0)
-    if (p.bm == 64) {
-      if (p.bnt == 128) E2EP_PAIR1_W(128, 64);
-      else E2EP_PAIR1_W(64, 64);
+    lp_bwd_pair_launch(w, gout, res, dxv, dx_bytes, g, M, dp.lp, ws_dgrad, xv, wp, gr, part2, s, xb);
+  } else {
+    // k_conv_gemm data gradient: launch_gemm's grid and fold counters
+    const GemmPlan &p = dp.gp;
+    const dim3 g1(cdiv(p.ncols, p.bnt), cdiv(M, p.bm), p.nph * p.splits);
+    float *part1 = p.splits > 1 ? static_cast<float *>(ws_dgrad) : nullptr;
+    unsigned int *cnt = p.splits > 1 ? handoff_slots((int)g1.x * (int)g1.y, s) : nullptr;
+    if (kind == PAIR_GEMM1X1) {
+      const int nt2 = cdiv(g.Cout, wp.tm) * cdiv(g.Cin, wp.tn);
+      const dim3 grid(g1.x * g1.y * g1.z + nt2 * gr.used);
+      const int wfirst = g_tune[TUNE_PAIR1X1_ORDER] == 2 ? 1 : 0;
+      with_gemm_tile(p, [&](auto bt, auto bmt) {
+        with_tile2x2(wp.tm == 64, wp.tn == 64, [&](auto ti, auto tj) {
+          hipLaunchKernelGGL((k_conv_bwd_pair1x1<decltype(bt)::value, decltype(bmt)::value,
+                                                 decltype(ti)::value, decltype(tj)::value>),
+                             grid, dim3(256), 0, s, w, gout, res, dx, dx_bytes, g, M, p.splits, p.kper,
+                             part1, cnt, (int)g1.x, (int)g1.y, (int)g1.z, x, part2, gr.used, gr.per,
+                             nt2, wfirst);
+        });
+      });
     } else {
-      if (p.bnt == 256) E2EP_PAIR1_W(256, 32);
-      else E2EP_PAIR1_W(128, 32);
+      const dim3 g2(cdiv(g.Cin * tl.n, wp.tn), cdiv(g.Cout, wp.tm), gr.used);
+      const dim3 grid(g1.x * g1.y * g1.z + g2.x * g2.y * g2.z);
+      with_gemm_tile(p, [&](auto bt, auto bmt) {
+        hipLaunchKernelGGL((k_conv_bwd_pair<decltype(bt)::value, decltype(bmt)::value>), grid,
+                           dim3(256), 0, s, w, gout, res, dx, dx_bytes, g, M, p.splits, p.kper, part1,
+                           cnt, (int)g1.x, (int)g1.y, (int)g1.z, x, part2, gr.per, tl, (int)g2.x,
+                           (int)g2.y, (int)g2.z);
+      });
     }
-#undef E2EP_PAIR1_W
-#undef E2EP_PAIR1
     if (p.splits > 1 && !cnt)  // no fold counters: the data gradient's slabs reduced here
       hipLaunchKernelGGL(k_conv_reduce, dim3(cdiv(p.ncols, 256), M), dim3(256), 0, s, part1,
                          p.splits, M, g.H * g.W, (int)p.ncols, nullptr, 0, res, dx);
-    reduce_splits(part2, used, g.Cout * g.Cin, dw, 0, 1, 1ULL, s);
-    return launch_status("e2ep_conv_bwd");
-  } else {
-    // weight gradient grid (e2ep_conv_wgrad's k_conv_wgrad2 path)
-    const int Ptot = g.N * g.P * g.Q;
-    int per = (Ptot + wsplits - 1) / wsplits;
-    per = (per + W2K - 1) / W2K * W2K;
-    used = (Ptot + per - 1) / per;
-    const dim3 g2(cdiv(g.Cin * tl.n, 64), cdiv(g.Cout, 64), used);
-    const dim3 grid(g1.x * g1.y * g1.z + g2.x * g2.y * g2.z);
-#define E2EP_PAIR(BNTV, BMTV)                                                                     \
-  hipLaunchKernelGGL((k_conv_bwd_pair<BNTV, BMTV>), grid, dim3(256), 0, s, w, gout, res, dx,      \
-                     dx_bytes, g, M, p.splits, p.kper, part1, cnt, (int)g1.x, (int)g1.y,           \
-                     (int)g1.z, x, part2, per, tl, (int)g2.x, (int)g2.y, (int)g2.z)
-    if (p.bm == 64) {
-      if (p.bnt == 128) E2EP_PAIR(128, 64);
-      else E2EP_PAIR(64, 64);
-    } else {
-      if (p.bnt == 256) E2EP_PAIR(256, 32);
-      else E2EP_PAIR(128, 32);
-    }
-#undef E2EP_PAIR
   }
-  if (p.splits > 1 && !cnt)  // no fold counters: the data gradient's slabs reduced here
-    hipLaunchKernelGGL(k_conv_reduce, dim3(cdiv(p.ncols, 256), M), dim3(256), 0, s, part1,
-                       p.splits, M, g.H * g.W, (int)p.ncols, nullptr, 0, res, dx);
-  reduce_splits(part2, used, g.Cout * g.Cin * g.R * g.S, dw, 0, g.R * g.S, tl.mask, s);
+  reduce_splits(part2, gr.used, g.Cout * g.Cin * g.R * g.S, dw, 0, g.R * g.S, tl.mask, s);
   return launch_status("e2ep_conv_bwd");
 }
 

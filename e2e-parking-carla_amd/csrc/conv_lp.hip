@@ -490,12 +490,7 @@ __global__ void __launch_bounds__(256) k_conv_lp_reduce(
 }
 
 // ---- launch plan ---------------------------------------------------------------------------
-struct LpPlan {
-  int wm, wn, lk, splits, kper, nph;
-  long long ncols;  // columns of the largest phase
-};
-
-static LpPlan lp_plan(int mode, const ConvGeom &g, int M, int op) {
+LpPlan lp_plan(int mode, const ConvGeom &g, int M, int op) {
   LpPlan p;
   const int Kc = mode == 0 ? g.Cin : g.Cout;
   p.nph = mode ? g.sh * g.sw : 1;
@@ -590,11 +585,6 @@ bool lp_ok(int mode, const ConvGeom &g, int M, int op) {
   return M >= 40 && (g.R * g.S > 1 || Kc > LK);
 }
 
-size_t lp_workspace(int mode, const ConvGeom &g, int M, int op) {
-  const LpPlan p = lp_plan(mode, g, M, op);
-  return p.splits > 1 ? (size_t)p.splits * M * p.ncols * sizeof(float) : 0;
-}
-
 template <int MODE, int ACT, int OP, typename TS = float, typename TD = float>
 static void lp_tiles(const LpPlan &p, dim3 grid, hipStream_t s, const float *w, const TS *src,
                      const float *bias, TD *out, long long out_bytes, const ConvGeom &g, int M,
@@ -634,16 +624,9 @@ static void lp_tiles(const LpPlan &p, dim3 grid, hipStream_t s, const float *w, 
 #undef LP_L
 }
 
-int lp_stats_tiles(const ConvGeom &g, int op) {
-  const LpPlan p = lp_plan(0, g, g.Cout, op);
-  if (p.splits > 1 && g_tune[TUNE_SPLITK_FOLD] != 2) return 0;  // final values in the reduce
-  return (int)cdiv(p.ncols, 64 * p.wn);
-}
-
 int lp_launch(int mode, int act, int op, const float *w, const void *src, const float *bias,
-              void *dst, long long dst_bytes, const ConvGeom &g, int M, void *workspace,
-              hipStream_t s, double *stats, int io) {
-  const LpPlan p = lp_plan(mode, g, M, op);
+              void *dst, long long dst_bytes, const ConvGeom &g, int M, const LpPlan &p,
+              void *workspace, hipStream_t s, double *stats, int io) {
   const dim3 grid(cdiv(p.ncols, 64 * p.wn), cdiv(M, 64 * p.wm), p.nph * p.splits);
   float *part = nullptr;
   unsigned int *cnt = nullptr;
@@ -1058,132 +1041,98 @@ bool lp_wgrad_ok(const ConvGeom &g, const TapList &tl) {
   return g_tune[TUNE_LP_WGRAD_TILE] > 1 || (long long)g.Cout * g.Cin * tl.n >= 2048;
 }
 
-int lp_wgrad_splits(const ConvGeom &g, const TapList &tl, int op) {
+void lp_wgrad_plan(const ConvGeom &g, WgradPlan &p) {
   int wm, wn;
-  lp_wgrad_tile(g, tl, wm, wn);
-  const int lk = lp_wgrad_lk(g, op);
-  const long long tiles = (long long)cdiv(g.Cin * tl.n, 64 * wn) * cdiv(g.Cout, 64 * wm);
+  lp_wgrad_tile(g, p.tl, wm, wn);
+  p.tm = 64 * wm;
+  p.tn = 64 * wn;
+  p.kstep = lp_wgrad_lk(g, p.op);
+  const long long tiles = (long long)cdiv(g.Cin * p.tl.n, p.tn) * cdiv(g.Cout, p.tm);
   const long long pix = (long long)g.N * g.P * g.Q;
   const long long target = g_tune[TUNE_LPW_TARGET];  // workgroups aimed at (e2ep_tune key 22)
   long long s = (target + tiles - 1) / tiles;
-  s = std::min(s, std::max(1LL, pix / (std::max(256, 4 * lk))));  // >= 256 pixels per slab
-  return (int)std::max(1LL, std::min(s, 256LL));
+  s = std::min(s, std::max(1LL, pix / (std::max(256, 4 * p.kstep))));  // >= 256 pixels per slab
+  p.splits = (int)std::max(1LL, std::min(s, 256LL));
 }
 
-int lp_wgrad_launch(const float *gout, const void *xv, const ConvGeom &g, const TapList &tl,
-                    int splits, float *part, hipStream_t s, int op, bool xb) {
+void lp_wgrad_launch(const float *gout, const void *xv, const ConvGeom &g, const WgradPlan &p,
+                     WgradGrid gr, float *part, hipStream_t s, bool xb) {
   const float *x = static_cast<const float *>(xv);
   const bf16_t *xh = static_cast<const bf16_t *>(xv);
-  int wm, wn;
-  lp_wgrad_tile(g, tl, wm, wn);
-  const int lk = lp_wgrad_lk(g, op);
-  const int Ptot = g.N * g.P * g.Q;
-  int per = (Ptot + splits - 1) / splits;
-  per = (per + lk - 1) / lk * lk;
-  const int used = (Ptot + per - 1) / per;
-  const dim3 grid(cdiv(g.Cin * tl.n, 64 * wn), cdiv(g.Cout, 64 * wm), used);
-#define WL(WMV, WNV)                                                                             \
-  do {                                                                                           \
-    if (op != 1)                                                                                 \
-      hipLaunchKernelGGL((k_wgrad_lp<WMV, WNV, 0, 32>), grid, dim3(256), 0, s, gout, x, part, g, per, tl); \
-    else if (xb && lk == 64)                                                                     \
-      hipLaunchKernelGGL((k_wgrad_lp<WMV, WNV, 1, 64, bf16_t>), grid, dim3(256), 0, s, gout, xh, part, g, per, tl); \
-    else if (xb)                                                                                 \
-      hipLaunchKernelGGL((k_wgrad_lp<WMV, WNV, 1, 32, bf16_t>), grid, dim3(256), 0, s, gout, xh, part, g, per, tl); \
-    else if (lk == 64)                                                                           \
-      hipLaunchKernelGGL((k_wgrad_lp<WMV, WNV, 1, 64>), grid, dim3(256), 0, s, gout, x, part, g, per, tl); \
-    else                                                                                         \
-      hipLaunchKernelGGL((k_wgrad_lp<WMV, WNV, 1, 32>), grid, dim3(256), 0, s, gout, x, part, g, per, tl); \
-  } while (0)
-  if (wm == 2 && wn == 2) WL(2, 2);
-  else if (wm == 2) WL(2, 1);
-  else if (wn == 2) WL(1, 2);
-  else WL(1, 1);
-#undef WL
-  return used;
+  const TapList &tl = p.tl;
+  const int per = gr.per, lk = p.kstep;
+  const dim3 grid(cdiv(g.Cin * tl.n, p.tn), cdiv(g.Cout, p.tm), gr.used);
+  with_tile2x2(p.tm == 128, p.tn == 128, [&](auto wm, auto wn) {
+    constexpr int WM = decltype(wm)::value, WN = decltype(wn)::value;
+    if (p.op != 1)
+      hipLaunchKernelGGL((k_wgrad_lp<WM, WN, 0, 32>), grid, dim3(256), 0, s, gout, x, part, g, per, tl);
+    else if (xb && lk == 64)
+      hipLaunchKernelGGL((k_wgrad_lp<WM, WN, 1, 64, bf16_t>), grid, dim3(256), 0, s, gout, xh, part, g, per, tl);
+    else if (xb)
+      hipLaunchKernelGGL((k_wgrad_lp<WM, WN, 1, 32, bf16_t>), grid, dim3(256), 0, s, gout, xh, part, g, per, tl);
+    else if (lk == 64)
+      hipLaunchKernelGGL((k_wgrad_lp<WM, WN, 1, 64>), grid, dim3(256), 0, s, gout, x, part, g, per, tl);
+    else
+      hipLaunchKernelGGL((k_wgrad_lp<WM, WN, 1, 32>), grid, dim3(256), 0, s, gout, x, part, g, per, tl);
+  });
 }
 
 // ---- paired backward (k_lp_bwd_pair) ------------------------------------------------------
 // Instantiated pairs: fp32 (op 0) 64 x 64 data-gradient tiles with the 64 x 64 weight-gradient
 // tile; bf16 (op 1) data-gradient tiles 64 x 64, 128 x 64 and 64 x 128 with weight-gradient
 // tiles 64 / 128 x 64 / 128, 32-deep K-steps on both (the plans' defaults).
-static bool lp_pair_tiles(const ConvGeom &g, int M, int op, const TapList &tl, LpPlan &p,
-                          int &wwm, int &wwn) {
-  p = lp_plan(1, g, M, op);
-  if (p.lk != LK || (p.splits > 1 && g_tune[TUNE_SPLITK_FOLD] != 2)) return false;
-  if (op == 0) {
-    wwm = wwn = 1;
-    return p.wm == 1 && p.wn == 1 && (g.P * g.Q) % LK == 0;
-  }
+bool lp_bwd_pair_ok(const ConvGeom &g, LpPlan &p, const WgradPlan &wp) {
+  if (p.lk != LK || wp.kstep != LK || (p.splits > 1 && g_tune[TUNE_SPLITK_FOLD] != 2)) return false;
+  if (wp.op == 0)  // with the k_conv_wgrad2 plan (whole 32-pixel steps per image)
+    return wp.kind == WGRAD_GEN2 && p.wm == 1 && p.wn == 1;
   // not the 128 x 128 data-gradient tile: its ~200 VGPRs hold the whole paired grid to one
   // workgroup per SIMD, and the weight-gradient blocks then run at a third of their occupancy
   // (C3: 87 us paired against ~39 + 44 us overlapped on two streams).  Without a K split the
   // pair runs that data gradient on 128 x 64 tiles instead: every output's K order is the
   // same whatever the tile, so the results stay bitwise those of the two-launch path.
-  if (op == 1 && p.wm == 2 && p.wn == 2 && p.splits == 1) p.wn = 1;
-  if (op != 1 || p.wn > 2 || (p.wm == 2 && p.wn == 2) || !lp_wgrad_ok(g, tl) ||
-      lp_wgrad_lk(g, op) != LK)
-    return false;
-  lp_wgrad_tile(g, tl, wwm, wwn);
-  return true;
+  if (p.wm == 2 && p.wn == 2 && p.splits == 1) p.wn = 1;
+  return wp.kind == WGRAD_LP && p.wn <= 2 && !(p.wm == 2 && p.wn == 2);
 }
 
-bool lp_bwd_pair_ok(const ConvGeom &g, int M, int op, const TapList &tl) {
-  LpPlan p;
-  int wwm, wwn;
-  return lp_pair_tiles(g, M, op, tl, p, wwm, wwn);
-}
-
-int lp_bwd_pair_launch(const float *w, const float *gout, const float *res, void *dxv,
-                       long long dx_bytes, const ConvGeom &g, int M, int op, void *ws_dgrad,
-                       const void *xv, const TapList &tl, int wsplits, float *part2,
-                       hipStream_t s, bool xb) {
-  LpPlan p;
-  int wwm, wwn;
-  if (!lp_pair_tiles(g, M, op, tl, p, wwm, wwn)) return -1;
-  if (xb && op != 1) return -1;
+void lp_bwd_pair_launch(const float *w, const float *gout, const float *res, void *dxv,
+                        long long dx_bytes, const ConvGeom &g, int M, const LpPlan &p,
+                        void *ws_dgrad, const void *xv, const WgradPlan &wp, WgradGrid gr,
+                        float *part2, hipStream_t s, bool xb) {
   float *dx = static_cast<float *>(dxv);
   const float *x = static_cast<const float *>(xv);
   bf16_t *dxh = static_cast<bf16_t *>(dxv);
   const bf16_t *xh = static_cast<const bf16_t *>(xv);
+  const TapList &tl = wp.tl;
+  const int per = gr.per;
   const dim3 g1(cdiv(p.ncols, 64 * p.wn), cdiv(M, 64 * p.wm), p.nph * p.splits);
   float *part1 = p.splits > 1 ? static_cast<float *>(ws_dgrad) : nullptr;
   unsigned int *cnt = p.splits > 1 ? handoff_slots((int)g1.x * (int)g1.y, s) : nullptr;
-  const int Ptot = g.N * g.P * g.Q;
-  int per = (Ptot + wsplits - 1) / wsplits;
-  per = (per + LK - 1) / LK * LK;
-  const int used = (Ptot + per - 1) / per;
-  const dim3 g2(cdiv(g.Cin * tl.n, 64 * wwn), cdiv(g.Cout, 64 * wwm), used);
+  const dim3 g2(cdiv(g.Cin * tl.n, wp.tn), cdiv(g.Cout, wp.tm), gr.used);
   const dim3 grid(g1.x * g1.y * g1.z + g2.x * g2.y * g2.z);
-#define PAIR_L(DM, DN, OPV, WMV, WNV)                                                           \
-  do {                                                                                          \
-    if (OPV == 1 && xb)                                                                         \
-      hipLaunchKernelGGL((k_lp_bwd_pair<DM, DN, OPV, WMV, WNV, bf16_t>), grid, dim3(256), 0, s, w, \
-                         gout, res, dxh, dx_bytes, g, M, p.splits, p.kper, part1, cnt, (int)g1.x, \
-                         (int)g1.y, (int)g1.z, xh, part2, per, tl, (int)g2.x, (int)g2.y, (int)g2.z); \
-    else                                                                                        \
-      hipLaunchKernelGGL((k_lp_bwd_pair<DM, DN, OPV, WMV, WNV>), grid, dim3(256), 0, s, w, gout,  \
-                         res, dx, dx_bytes, g, M, p.splits, p.kper, part1, cnt, (int)g1.x,       \
-                         (int)g1.y, (int)g1.z, x, part2, per, tl, (int)g2.x, (int)g2.y, (int)g2.z); \
-  } while (0)
-#define PAIR_W(DM, DN)                                     \
-  do {                                                     \
-    if (wwm == 2 && wwn == 2) PAIR_L(DM, DN, 1, 2, 2);     \
-    else if (wwm == 2) PAIR_L(DM, DN, 1, 2, 1);            \
-    else if (wwn == 2) PAIR_L(DM, DN, 1, 1, 2);            \
-    else PAIR_L(DM, DN, 1, 1, 1);                          \
-  } while (0)
-  if (op == 0) PAIR_L(1, 1, 0, 1, 1);
-  else if (p.wm == 2) PAIR_W(2, 1);
-  else if (p.wn == 2) PAIR_W(1, 2);
-  else PAIR_W(1, 1);
-#undef PAIR_W
-#undef PAIR_L
+  auto pair = [&](auto dm, auto dn, auto opc, auto wm, auto wn) {
+    constexpr int DM = decltype(dm)::value, DN = decltype(dn)::value, OP = decltype(opc)::value;
+    constexpr int WM = decltype(wm)::value, WN = decltype(wn)::value;
+    if (OP == 1 && xb)
+      hipLaunchKernelGGL((k_lp_bwd_pair<DM, DN, OP, WM, WN, bf16_t>), grid, dim3(256), 0, s, w,
+                         gout, res, dxh, dx_bytes, g, M, p.splits, p.kper, part1, cnt, (int)g1.x,
+                         (int)g1.y, (int)g1.z, xh, part2, per, tl, (int)g2.x, (int)g2.y, (int)g2.z);
+    else
+      hipLaunchKernelGGL((k_lp_bwd_pair<DM, DN, OP, WM, WN>), grid, dim3(256), 0, s, w, gout,
+                         res, dx, dx_bytes, g, M, p.splits, p.kper, part1, cnt, (int)g1.x,
+                         (int)g1.y, (int)g1.z, x, part2, per, tl, (int)g2.x, (int)g2.y, (int)g2.z);
+  };
+  auto pair_w = [&](auto dm, auto dn) {  // bf16: every k_wgrad_lp tile
+    with_tile2x2(wp.tm == 128, wp.tn == 128,
+                 [&](auto wm, auto wn) { pair(dm, dn, IntC<1>(), wm, wn); });
+  };
+  if (wp.op == 0) pair(IntC<1>(), IntC<1>(), IntC<0>(), IntC<1>(), IntC<1>());
+  else if (p.wm == 2) pair_w(IntC<2>(), IntC<1>());
+  else if (p.wn == 2) pair_w(IntC<1>(), IntC<2>());
+  else pair_w(IntC<1>(), IntC<1>());
   if (p.splits > 1 && !cnt)  // no fold counters: the data gradient's slabs reduced here
     hipLaunchKernelGGL(k_conv_lp_reduce, dim3(cdiv(p.ncols, 256), M), dim3(256), 0, s,
                        static_cast<const float *>(part1), p.splits, M, g.H * g.W, (int)p.ncols,
                        nullptr, 0, res, dx);
-  return used;
 }
 
 }  // namespace e2ep

@@ -14,9 +14,11 @@
 // launch keeps its range on every replay (kernels of one graph replay never overlap
 // themselves).  Launches captured into a graph take their ranges from a region that is
 // handed out once (HANDOFF_CAPTURED counters, never reused while the process lives; once they
-// run out, ~500 captured train steps, later captures get none and use separate reduce
-// launches); eager launches rotate through the other region, so an eager launch never shares
-// a slot with a live graph's launch.
+// run out, ~500 captured train steps, later captures get none: a plain split-K launch then
+// runs its reduction as a separate launch, but a conv forward with fused BatchNorm statistics
+// and a bf16 data gradient need the in-launch fold and return E2EP_EINVAL, conv.hip /
+// conv_lp.hip, so such a capture fails); eager launches rotate through the other region, so an
+// eager launch never shares a slot with a live graph's launch.
 #pragma once
 #include "common.h"
 
@@ -26,8 +28,9 @@ constexpr int HANDOFF_POOL = 1 << 24;      // counters in a device's pool (64 MB
 constexpr int HANDOFF_CAPTURED = 15 << 20; // of them for launches captured into graphs
 
 // n zeroed counters for one launch on `stream` (host; the current device's pool), or nullptr
-// when n is out of range or the pool cannot be fetched: the callers then run their split-K
-// reductions as separate launches
+// when n is out of range, the pool cannot be fetched or the captured region is used up: the
+// callers then run their split-K reductions as separate launches, or return E2EP_EINVAL where
+// the launch needs the fold (statistics, bf16 data gradient)
 unsigned int *handoff_slots(int n, hipStream_t stream);
 
 __device__ __forceinline__ void st_sc1(float *p, float v) {

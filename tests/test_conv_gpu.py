@@ -471,3 +471,118 @@ def test_conv_bwd_pair_covers_small_map_layers():
         with precision.use(mode):
             ok = [lib.e2ep_conv_bwd_pair_ok(_lib.dims(d), d[1]) for d in d3]
         assert all(ok), (mode, ok)
+
+
+# The smallest shapes that reach each kind of launch plan (csrc/conv.hip conv_plan / wgrad_plan):
+# (N, Cin, H, W, Cout, K, stride, pad, dil, grad_channels)
+PLAN_SHAPES = {
+    "k3": (2, 64, 16, 16, 64, 3, 1, 1, 1, None),
+    "k1_to24": (2, 48, 16, 16, 24, 1, 1, 0, 1, None),
+    "k1_to96": (2, 48, 16, 16, 96, 1, 1, 0, 1, None),
+    "stem": (1, 65, 32, 32, 64, 7, 2, 3, 1, 64),
+    "dil24": (1, 64, 16, 16, 64, 3, 1, 24, 24, None),
+    "direct": (1, 3, 32, 32, 48, 3, 2, 0, 1, None),
+}
+# (precision mode, e2ep_tune keys on top of it): key 14 / 15 = fp32 k_conv_lp / k_wgrad_lp
+PLAN_SETTINGS = {"fp32": ("fp32", {}), "bf16": ("bf16", {}), "fp32_lp": ("fp32", {14: 2, 15: 2})}
+_PLAN_REF = {}
+
+
+def _plan_ref(name):
+    """Inputs and fp64 references of a PLAN_SHAPES entry, computed once: with the operands as
+    they are (fp32 kernels) and rounded to bf16 (C3's kernels multiply rounded operands
+    exactly and accumulate in fp32, as test_conv_low_precision_operands)."""
+    if name in _PLAN_REF:
+        return _PLAN_REF[name]
+    N, Cin, H, W, Cout, K, st, pad, dil, gc = PLAN_SHAPES[name]
+    g = torch.Generator().manual_seed(97 + Cin + Cout)
+    x = torch.randn(N, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, K, K, generator=g) / (Cin * K * K) ** 0.5
+    P = (H + 2 * pad - dil * (K - 1) - 1) // st + 1
+    gy = torch.randn(N, Cout, P, P, generator=g)
+    ref = {"x": x, "w": w, "gy": gy}
+    for tag, r in (("fp32", lambda t: t.double()), ("bf16", lambda t: t.to(torch.bfloat16).double())):
+        xr, wr = r(x).requires_grad_(True), r(w).requires_grad_(True)
+        y = F.conv2d(xr, wr, None, st, pad, dil)
+        y.backward(r(gy))
+        ref[tag] = (y.detach(), xr.grad[:, :gc or Cin], wr.grad)
+    _PLAN_REF[name] = ref
+    return ref
+
+
+@pytest.mark.parametrize("setting", list(PLAN_SETTINGS))
+@pytest.mark.parametrize("shape", list(PLAN_SHAPES))
+def test_conv_queries_agree_with_launches(shape, setting):
+    """Forward, data gradient, weight gradient and (where e2ep_conv_bwd_pair_ok) the paired
+    backward through the C ABI, every workspace of exactly the queried size and the statistics
+    buffer of exactly Cout x tiles x 2 doubles: every call returns 0, the results stay within
+    the fp64 bounds of test_conv_fwd_bwd_vs_fp64 (fp32: 2e-6) and
+    test_conv_low_precision_operands (bf16, against rounded operands: 2e-6, weight gradient
+    5e-6), and the paired results are bitwise the two launches'."""
+    import ctypes
+    from e2ep_amd import _lib, precision
+    lib = _lib.load()
+    N, Cin, H, W, Cout, K, st, pad, dil, gc = PLAN_SHAPES[shape]
+    mode, tune = PLAN_SETTINGS[setting]
+    ref = _plan_ref(shape)
+    P = ref["gy"].shape[2]
+    M = gc or Cin
+    d = _lib.dims((N, Cin, H, W, Cout, K, K, P, P, st, st, pad, pad, dil, dil))
+    x, gy = ref["x"].to(DEV), ref["gy"].to(DEV)
+    wt = ref["w"].permute(2, 3, 0, 1).reshape(K * K, Cout, Cin).contiguous().to(DEV)  # tap-major
+
+    def buf(nbytes):
+        return torch.empty(nbytes, dtype=torch.uint8, device=DEV) if nbytes else None
+
+    def ok(rc, what):
+        assert rc == 0, (what, rc, lib.e2ep_last_error().decode())
+
+    old = {k: lib.e2ep_tune(k, v) for k, v in tune.items()}
+    try:
+        with precision.use(mode):
+            s = _lib.stream()
+            ws = buf(lib.e2ep_conv_fwd_workspace(d))
+            tiles = lib.e2ep_conv_fwd_stats_tiles(d, 1)
+            y = torch.empty(N, Cout, P, P, device=DEV)
+            stats = torch.empty(Cout * tiles * 2, dtype=torch.float64, device=DEV) if tiles > 0 else None
+            if tiles > 0:
+                ok(lib.e2ep_conv_fwd_stats(_lib.ptr(x), _lib.ptr(wt), None, d, 0, 1, _lib.ptr(y), _lib.ptr(ws),
+                                           _lib.nbytes(ws), _lib.ptr(stats), _lib.nbytes(stats), s, 0), "fwd_stats")
+            else:
+                ok(lib.e2ep_conv_fwd(_lib.ptr(x), _lib.ptr(wt), None, d, 0, 1, _lib.ptr(y), _lib.ptr(ws),
+                                     _lib.nbytes(ws), s, 0), "fwd")
+            wsd = buf(lib.e2ep_conv_dgrad_workspace(d, M))
+            dx = torch.empty(N, M, H, W, device=DEV)
+            ok(lib.e2ep_conv_dgrad_acc(_lib.ptr(gy), _lib.ptr(wt), d, M, 1, None, _lib.ptr(dx), _lib.ptr(wsd),
+                                       _lib.nbytes(wsd), s, 0), "dgrad")
+            splits = lib.e2ep_conv_wgrad_splits(d)
+            wsw = buf(lib.e2ep_conv_wgrad_workspace(d, splits))
+            dw = torch.empty(Cout, Cin, K, K, device=DEV)
+            ok(lib.e2ep_conv_wgrad(_lib.ptr(gy), _lib.ptr(x), d, splits, _lib.ptr(wsw), _lib.nbytes(wsw),
+                                   _lib.ptr(dw), 0, s, 0), "wgrad")
+            pair = None
+            if lib.e2ep_conv_bwd_pair_ok(d, M):
+                dx2, dw2 = torch.empty_like(dx), torch.empty_like(dw)
+                wsd2, wsw2 = buf(_lib.nbytes(wsd)), buf(_lib.nbytes(wsw))
+                ok(lib.e2ep_conv_bwd(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(wt), d, M, None, _lib.ptr(dx2),
+                                     _lib.ptr(wsd2), _lib.nbytes(wsd2), splits, _lib.ptr(wsw2),
+                                     _lib.nbytes(wsw2), _lib.ptr(dw2), s, 0), "bwd pair")
+                pair = (dx2, dw2)
+            torch.cuda.synchronize()
+    finally:
+        for k, v in old.items():
+            lib.e2ep_tune(k, v)
+    y64, dx64, dw64 = ref[mode]
+    # the direct kernel (tiny Cin x R x S) multiplies fp32 operands in every mode
+    fwd_ref = ref["fp32"][0] if shape == "direct" else y64
+    errs = (rel_l2(y, fwd_ref), rel_l2(dx, dx64), rel_l2(dw, dw64))
+    print(shape, setting, "tiles", tiles, "splits", splits, "pair", pair is not None, "rel-L2", errs)
+    assert errs[0] < 2e-6 and errs[1] < 2e-6
+    assert errs[2] < (5e-6 if mode == "bf16" else 2e-6)
+    if tiles > 0:  # part[(tile * Cout + c) * 2 + {sum, sum of squares}]: test_bn_stats_gpu's bounds
+        part = stats.view(tiles, Cout, 2).sum(0).cpu()
+        yd = y.double().cpu().transpose(0, 1).reshape(Cout, -1)
+        assert torch.allclose(part[:, 0], yd.sum(1), rtol=2e-7, atol=2e-7 * yd.abs().sum().item() / Cout)
+        assert torch.allclose(part[:, 1], (yd * yd).sum(1), rtol=2e-7, atol=0)
+    if pair is not None:
+        assert torch.equal(pair[0], dx) and torch.equal(pair[1], dw)
