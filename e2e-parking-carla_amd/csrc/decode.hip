@@ -11,6 +11,10 @@
 // it into the reference's tensors in the same pass.  HBM-bound byte work:
 // one thread per 4 pixels (3 dword loads of packed RGB, float4 / double2 stores), 26 bytes
 // of traffic per camera pixel (6 read, 12 + 8 written).
+//
+// The closed-loop agent has no cache: its frames arrive as raw BGRA sensor bytes
+// (agent/parking_agent.py:458-465, four ProcessImage calls per tick).  k_decode_bgra crops
+// and normalises them straight from the uploaded bytes with the same arithmetic.
 #include "common.h"
 
 namespace e2ep {
@@ -19,6 +23,14 @@ constexpr int DEC_THREADS = 256;
 
 __device__ __forceinline__ unsigned byte_of(const unsigned w[3], int k) {
   return (w[k >> 2] >> ((k & 3) * 8)) & 0xffu;
+}
+
+// torchvision ToTensor + Normalize of one uint8 value of channel c (0 = R): / 255, minus the
+// ImageNet mean, over the ImageNet std, three fp32 roundings in that order.  The one statement
+// of this arithmetic: the cached-crop decode and the raw BGRA decode both call it.
+__device__ __forceinline__ float normalise_u8(unsigned byte, int c) {
+  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+  return ((float)byte / 255.f - mean[c]) / stdv[c];
 }
 
 // rgb/depth_rgb [*][hw][3] uint8 (either may be null); output frame f reads source frame
@@ -37,10 +49,9 @@ __global__ void __launch_bounds__(DEC_THREADS)
   const long long sq = (src ? src[frame] : frame) * (hw / 4) + off / 4;
   if (rgb) {
     const unsigned w[3] = {rgb[3 * sq], rgb[3 * sq + 1], rgb[3 * sq + 2]};
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     for (int c = 0; c < 3; ++c) {
       float v[4];
-      for (int j = 0; j < 4; ++j) v[j] = ((float)byte_of(w, 3 * j + c) / 255.f - mean[c]) / stdv[c];
+      for (int j = 0; j < 4; ++j) v[j] = normalise_u8(byte_of(w, 3 * j + c), c);
       *reinterpret_cast<float4 *>(image + (frame * 3 + c) * hw + off) =
           make_float4(v[0], v[1], v[2], v[3]);
     }
@@ -57,6 +68,63 @@ __global__ void __launch_bounds__(DEC_THREADS)
     double2 *o = reinterpret_cast<double2 *>(depth + frame * hw + off);
     o[0] = make_double2(d[0], d[1]);
     o[1] = make_double2(d[2], d[3]);
+  }
+}
+
+// Raw sensor frames: bgra [N][H][W] dwords (B, G, R, A bytes: a CARLA image's raw_data), the
+// centred crop x crop window at (top, left) -> image [N][3][crop][crop] fp32 normalised and,
+// when rgb is not null, the uint8 crop [N][crop][crop][3].  One thread per V consecutive
+// pixels of a crop row: V dword loads (a pixel is one aligned dword), then per channel one
+// V-float store and V * 3 packed RGB bytes, all contiguous along the row across the wave.
+// V = 4 needs crop % 4 == 0 (16-byte image stores, dword RGB stores); V = 1 is the general path.
+template <int V>
+__global__ void __launch_bounds__(DEC_THREADS)
+    k_decode_bgra(const unsigned *__restrict__ bgra, long long groups, int H, int W, int crop,
+                  int top, int left, float *__restrict__ image,
+                  unsigned char *__restrict__ rgb) {
+  const long long g = (long long)blockIdx.x * DEC_THREADS + threadIdx.x;
+  if (g >= groups) return;
+  const int gpr = crop / V;  // groups per crop row
+  const long long row = g / gpr;
+  const int c0 = (int)(g - row * gpr) * V;
+  const long long n = row / crop;
+  const int r = (int)(row - n * crop);
+  const unsigned *src = bgra + (n * H + top + r) * W + left + c0;
+  unsigned w[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) w[j] = src[j];
+  const long long plane = (long long)crop * crop;
+  const long long o = (long long)r * crop + c0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float v[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = normalise_u8((w[j] >> (8 * (2 - c))) & 0xffu, c);
+    float *dst = image + (n * 3 + c) * plane + o;
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      dst[0] = v[0];
+    }
+  }
+  if (!rgb) return;
+  unsigned char *out = rgb + (n * plane + o) * 3;
+  if constexpr (V == 4) {
+    // 12 bytes R G B R G B ... from four B G R A dwords
+    unsigned p[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      const unsigned b = (w[k / 3] >> (8 * (2 - k % 3))) & 0xffu;
+      p[k >> 2] |= b << ((k & 3) * 8);
+    }
+    unsigned *o32 = reinterpret_cast<unsigned *>(out);
+    o32[0] = p[0];
+    o32[1] = p[1];
+    o32[2] = p[2];
+  } else {
+    out[0] = (unsigned char)((w[0] >> 16) & 0xffu);
+    out[1] = (unsigned char)((w[0] >> 8) & 0xffu);
+    out[2] = (unsigned char)(w[0] & 0xffu);
   }
 }
 
@@ -96,6 +164,32 @@ int e2ep_decode_frames(const void *rgb, const void *depth_rgb, const long long *
                      as_stream(stream), static_cast<const unsigned *>(rgb),
                      static_cast<const unsigned *>(depth_rgb), src_frame, quads, hw, image, depth);
   return launch_status("e2ep_decode_frames");
+}
+
+int e2ep_decode_bgra(const void *bgra, int N, int H, int W, int crop, float *image, void *rgb,
+                     void *stream) {
+  E2EP_REQUIRE(bgra && image, E2EP_EINVAL, "e2ep_decode_bgra: null buffer");
+  E2EP_REQUIRE(N > 0 && H > 0 && W > 0 && crop > 0, E2EP_EINVAL,
+               "e2ep_decode_bgra: bad shape (N=%d H=%d W=%d crop=%d)", N, H, W, crop);
+  E2EP_REQUIRE(crop <= H && crop <= W, E2EP_EINVAL,
+               "e2ep_decode_bgra: crop %d larger than the %d x %d frame", crop, H, W);
+  E2EP_REQUIRE(((uintptr_t)bgra & 3) == 0 && ((uintptr_t)image & 3) == 0, E2EP_EINVAL,
+               "e2ep_decode_bgra: misaligned buffer");
+  const int top = H / 2 - crop / 2, left = W / 2 - crop / 2;
+  const bool quad = crop % 4 == 0 && ((uintptr_t)image & 15) == 0 && ((uintptr_t)rgb & 3) == 0;
+  const long long groups = (long long)N * crop * (crop / (quad ? 4 : 1));
+  E2EP_REQUIRE(groups <= 0x7fffffffLL * DEC_THREADS, E2EP_ERANGE,
+               "e2ep_decode_bgra: %lld pixel groups exceed one grid", groups);
+  const dim3 grid(cdiv(groups, DEC_THREADS)), block(DEC_THREADS);
+  const unsigned *src = static_cast<const unsigned *>(bgra);
+  unsigned char *out = static_cast<unsigned char *>(rgb);
+  if (quad)
+    hipLaunchKernelGGL(k_decode_bgra<4>, grid, block, 0, as_stream(stream), src, groups, H, W,
+                       crop, top, left, image, out);
+  else
+    hipLaunchKernelGGL(k_decode_bgra<1>, grid, block, 0, as_stream(stream), src, groups, H, W,
+                       crop, top, left, image, out);
+  return launch_status("e2ep_decode_bgra");
 }
 
 int e2ep_widen_u8_i64(const void *src, const long long *src_row, long long rows, int row_len,

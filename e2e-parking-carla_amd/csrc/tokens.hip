@@ -15,6 +15,7 @@
 //
 // Dropout: keep(i) = att_keep(seed, i) for the output element index i (dropout.h), scaled by
 // 1 / (1 - p); p = 0 is the identity (eval, and the deterministic-train protocol).
+#include "argmax.h"
 #include "common.h"
 #include "dropout.h"
 
@@ -162,14 +163,8 @@ __global__ void __launch_bounds__(256) k_embed_tokens_bwd(
 // value), the token written into column `pos` of the persistent sequence.  Block per row; the
 // max and the sum reduce in a fixed order (deterministic).  A row holding a NaN or a +inf, or
 // only -inf, has NaN probabilities; torch.argmax ranks NaN above every number, so the order
-// below does too (the first NaN wins) and the token stays inside [0, V).
-__device__ __forceinline__ bool argmax_beats(float a, int ai, float b, int bi) {
-  const bool an = a != a, bn = b != b;
-  if (an != bn) return an;
-  if (an) return ai < bi;
-  return a > b || (a == b && ai < bi);
-}
-
+// below (argmax_beats, argmax.h) does too (the first NaN wins) and the token stays inside
+// [0, V).
 __global__ void __launch_bounds__(256) k_token_argmax_append(const float *__restrict__ logits,
                                                              long long rstride, int V,
                                                              int64_t *__restrict__ seq,

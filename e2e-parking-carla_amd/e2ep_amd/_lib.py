@@ -160,6 +160,12 @@ SIGNATURES = {
     "e2ep_decode_frames": (_i, [_p, _p, _p, _i64, _i, _p, _p, _p]),
     "e2ep_widen_u8_i64": (_i, [_p, _p, _i64, _i, _p, _p]),
     "e2ep_depth_bce_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "e2ep_decode_bgra": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
+    "e2ep_slot_stats_workspace": (_sz, [_i, _i]),
+    "e2ep_slot_partials": (_i, [_p, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "e2ep_slot_finish": (_i, [_p, _sz, _i, _i, _i, _d, _d, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p,
+                              _p]),
+    "e2ep_target_select": (_i, [_p, _p, _i, _p, _p]),
 }
 
 _LIB = None

@@ -932,6 +932,62 @@ int e2ep_widen_u8_i64(const void *src, const long long *src_row, long long rows,
                       long long *dst, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The closed-loop agent's per-frame host work (agent/parking_agent.py), on the device.
+ * Additive entry points (the ABI version stays 4); every launch is capturable.
+ *
+ *  - e2ep_decode_bgra: ProcessImage on a CARLA sensor image (dataset/carla_dataset.py:494-515
+ *    called four times by get_model_data, agent/parking_agent.py:458-465: BGRA bytes -> PIL
+ *    -> centred crop -> ToTensor -> Normalize).  bgra [N][H][W][4] uint8 (B, G, R, A) ->
+ *    image [N][3][crop][crop] fp32, the arithmetic of e2ep_decode_frames (bit-identical to
+ *    the reference), and, when rgb is not NULL, the uint8 crop [N][crop][crop][3] the agent
+ *    keeps for display.  Crop origin top = H/2 - crop/2, left = W/2 - crop/2
+ *    (scale_and_crop_image at scale 1).  crop > H or crop > W is E2EP_EINVAL (the reference
+ *    would return a smaller image); bgra and image 4-byte aligned.
+ *
+ *  - e2ep_slot_partials + e2ep_slot_finish: save_prev_target (agent/parking_agent.py:290-311),
+ *    get_target_point_ego_coord (:313-318), save_seg_img (:272-281) and detokenize
+ *    (dataset/carla_dataset.py:90-111).
+ *    e2ep_slot_partials: logits (B, C, X, Y) fp32 with element strides, 2 <= C <= 8.  Every
+ *    pixel's class is torch.argmax's (first index of the largest value; a NaN ranks above
+ *    every number, the first NaN wins); each workgroup of grid (row bands, B) writes int32
+ *    partials (count, sum of X-1-r, sum of c) over its pixels of target_class into
+ *    `workspace` (e2ep_slot_stats_workspace(B, X) bytes) — the row index is that of the
+ *    image flipped top to bottom, as the reference flips before it scans.  class_image
+ *    (optional) [B][X][Y] uint8 receives the flipped class image, class k stored as
+ *    class_lut[k] (class_lut: HOST array of C bytes, read at call time; {0, 128, 255} for the
+ *    agent).  16-byte loads along Y when Y % 4 == 0, stride_y == 1 and the pointer and other
+ *    strides are 16-byte multiples, dword loads otherwise: the same integers either way.
+ *    X * Y * max(X, Y) > INT32_MAX or B > 65535: E2EP_ERANGE.
+ *    e2ep_slot_finish: one wave per sample sums its partials in int64; when count > 0,
+ *    tx = sum(X-1-r) / count and ty = sum(c) / count by integer division (= int(np.average)),
+ *    px = (float)(-(tx - X/2.0) * res_x), py = (float)((ty - X/2.0) * res_y) in float64 (the
+ *    reference subtracts shape[0] / 2 on both axes) and state[b] = (1, px, py); when
+ *    count == 0 state[b] is left untouched.  state [B][3] fp32 (valid, px, py) persists
+ *    between calls; zero it to reset (init_agent's pre_target_point = None).  found [B] int32
+ *    and stats [B][3] int64 (count, tx, ty; tx = ty = -1 when count == 0) are optional.
+ *    When seq is not NULL the same launch detokenizes the int64 token row
+ *    seq[b * seq_stride + first .. first + 2] into controls [B][4] float64 (throttle, brake,
+ *    steer, reverse as 0 / 1) with half = (token_nums - 4) / 2, strict >, brake = -acc, and
+ *    copies the row's seq_len tokens into tokens_out [B][seq_len] (either may be NULL).
+ *
+ *  - e2ep_target_select: get_model_data (agent/parking_agent.py:474-476).
+ *    target[b] = state[b].valid ? (px, py, goal[b][2]) : goal[b]; goal, target [B][3] fp32.
+ * ------------------------------------------------------------------------------------- */
+int e2ep_decode_bgra(const void *bgra, int N, int H, int W, int crop, float *image, void *rgb,
+                     void *stream);
+size_t e2ep_slot_stats_workspace(int B, int X);
+int e2ep_slot_partials(const float *logits, long long stride_b, long long stride_c,
+                       long long stride_x, long long stride_y, int B, int C, int X, int Y,
+                       int target_class, const unsigned char *class_lut, void *class_image,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int e2ep_slot_finish(const void *workspace, size_t workspace_bytes, int B, int X, int Y,
+                     double res_x, double res_y, float *state, int32_t *found, int64_t *stats,
+                     const int64_t *seq, int seq_stride, int seq_len, int first, int token_nums,
+                     double *controls, int64_t *tokens_out, void *stream);
+int e2ep_target_select(const float *state, const float *goal, int B, float *target,
+                       void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * HIP-graph surgery: replace every memset node of a captured (not yet instantiated)
  * hipGraph_t by an equivalent kernel node.  Memset nodes replay incorrectly after the first
  * launch on this ROCm stack; PyTorch's reductions capture them.  `replaced` (optional)
