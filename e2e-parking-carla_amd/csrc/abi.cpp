@@ -25,8 +25,10 @@ void set_error(const char *fmt, ...) {
 // one camera-encoder BN weight), and the fp32 data gradient (mask 8) alone is neutral, so fp32
 // stays on the implicit GEMMs; the direct weight gradient (mask 4) is neutral in C3 and slower
 // than k_conv_wgrad2 in fp32 (profiles/r06/stem_direct_ab.txt).  Key 36 = 2: the 16x16 MBConv
-// middle in one launch per direction (mbconv_mid.hip; profiles/mbconv_mid/).
-int g_tune[TUNE_N] = {8192, 4096, 512, 512, 768, 1024, 512, 1, 1, 2, 1, 2, 2, 1, 2, 1, 1, 1, 1, 1, 1, 2, 1024, 2, 2048, 2, 1, 1, 2, 1, 2, 1, 1, 1, 1, 4, 2};
+// middle in one launch per direction (mbconv_mid.hip; profiles/mbconv_mid/).  Key 37 = 2: the
+// parameter-gradient finishing launches of a train step deferred to one batched launch per
+// kind after the backward (pgrad.hip; profiles/pgrad_defer/).
+int g_tune[TUNE_N] = {8192, 4096, 512, 512, 768, 1024, 512, 1, 1, 2, 1, 2, 2, 1, 2, 1, 1, 1, 1, 1, 1, 2, 1024, 2, 2048, 2, 1, 1, 2, 1, 2, 1, 1, 1, 1, 4, 2, 2};
 }  // namespace e2ep
 
 extern "C" {

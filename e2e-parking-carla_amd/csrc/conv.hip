@@ -30,6 +30,7 @@
 #include "gemm.h"
 #include "bnstats.h"
 #include "handoff.h"
+#include "pgrad.h"
 
 // Contraction only within one expression (a*b + c -> fma): the fp32 and bf16-storage
 // instantiations of a kernel (E2EP_IO_*) then fuse the same operations and round alike —
@@ -1286,79 +1287,41 @@ __global__ void __launch_bounds__(256, 2) k_conv_bwd_pair1x1(
   }
 }
 
-// fixed-order sum of the split slabs (+ optional accumulate into an existing gradient).
-// Block = 64 outputs x 16 split lanes: thread (o, r) sums splits r, r+16, ... with 4
-// independent chains, then the 16 lane sums are added in order through LDS.
-// Entries i whose tap (i % RS) is not live in `mask` are never written by the GEMM: their
-// result is 0 (a weight tap that only ever meets zero padding).
+// fixed-order sum of the split slabs (+ optional accumulate into an existing gradient): one
+// block of reduce_splits_block (pgrad.h, shared with the deferred batched launch) per 64 outputs
 __global__ void __launch_bounds__(1024) k_reduce_splits(const float *__restrict__ part, int splits,
                                                         int n, float *__restrict__ out,
                                                         int accumulate, int RS,
                                                         unsigned long long mask) {
   __shared__ float red[16][64];
-  const int o = threadIdx.x & 63, r = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + o;
-  const bool live = (mask >> (i % RS)) & 1ULL;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (i < n && live) {
-    int k = r;
-    for (; k + 48 < splits; k += 64) {
-      s0 += part[(size_t)(k + 0) * n + i];
-      s1 += part[(size_t)(k + 16) * n + i];
-      s2 += part[(size_t)(k + 32) * n + i];
-      s3 += part[(size_t)(k + 48) * n + i];
-    }
-    for (; k < splits; k += 16) s0 += part[(size_t)k * n + i];
-  }
-  red[r][o] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (r == 0 && i < n) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) s += red[j][o];
-    out[i] = accumulate ? out[i] + s : s;
-  }
+  reduce_splits_block(part, splits, n, out, accumulate, RS, mask, (int)blockIdx.x, red);
 }
 
-// The same reduction, four consecutive outputs per thread (n % 4 == 0): float4 loads of every
-// slab in split order, summed in that order.  The 16-lane tree above runs ~1.4 loads per
-// thread and left the launch latency-bound (15 us for the 13.5 MB of slabs of a 16x16 1x1
-// conv's weight gradient, ~1 TB/s); here each thread keeps all its slab loads in flight.
+// The same reduction, four consecutive outputs per thread (n % 4 == 0): reduce_splits4_thread
+// (pgrad.h)
 __global__ void __launch_bounds__(256) k_reduce_splits4(const float *__restrict__ part, int splits,
                                                          int n, float *__restrict__ out,
                                                          int accumulate, int RS,
                                                          unsigned long long mask) {
   const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (i >= n) return;
-  float4 acc = *reinterpret_cast<const float4 *>(part + i);
-#pragma unroll 8
-  for (int k = 1; k < splits; ++k) {
-    const float4 v = *reinterpret_cast<const float4 *>(part + (size_t)k * n + i);
-    acc.x += v.x;
-    acc.y += v.y;
-    acc.z += v.z;
-    acc.w += v.w;
-  }
-  float r[4] = {acc.x, acc.y, acc.z, acc.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (!((mask >> ((i + e) % RS)) & 1ULL)) r[e] = 0.f;  // dead tap: never written by the GEMM
-  float4 o = make_float4(r[0], r[1], r[2], r[3]);
-  if (accumulate) {
-    const float4 a = *reinterpret_cast<const float4 *>(out + i);
-    o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
-  }
-  *reinterpret_cast<float4 *>(out + i) = o;
+  reduce_splits4_thread(part, splits, n, out, accumulate, RS, mask, i);
 }
 
 // fixed-order split-K reduction of the weight-gradient slabs: the float4 kernel when it has
 // enough threads to fill the chip (>= 32768: one per 4 outputs) and few slabs each; the split-
 // lane kernel otherwise (small weights with hundreds of slabs, e.g. the 1x1 weight gradients
-// of the 128x128 maps: one float4 thread per 4 outputs serialises those, 27 -> 39 us)
+// of the 128x128 maps: one float4 thread per 4 outputs serialises those, 27 -> 39 us).
+// Inside a deferral scope (pgrad.h) the launch is recorded instead, with that choice, and runs
+// in the batched kernel of e2ep_defer_flush: nothing reads a weight gradient before then.
 static void reduce_splits(const float *part, int splits, int n, float *out, int accumulate, int RS,
                           unsigned long long mask, hipStream_t s) {
-  if (n % 4 == 0 && n >= 131072 && splits <= 64 && (reinterpret_cast<uintptr_t>(part) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(out) & 15) == 0)
+  const bool f4 = n % 4 == 0 && n >= 131072 && splits <= 64 &&
+                  (reinterpret_cast<uintptr_t>(part) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  if (pgrad_defer(SlabRec{part, out, mask, n, splits, RS, (accumulate ? 1 : 0) | (f4 ? 2 : 0)}))
+    return;
+  if (f4)
     hipLaunchKernelGGL(k_reduce_splits4, dim3(cdiv(n / 4, 256)), dim3(256), 0, s, part, splits, n,
                        out, accumulate, RS, mask);
   else

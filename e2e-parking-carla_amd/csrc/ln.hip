@@ -11,6 +11,7 @@
 // kernel — deterministic.
 #include "common.h"
 #include "dropout.h"
+#include "pgrad.h"
 
 namespace e2ep {
 
@@ -130,28 +131,13 @@ __global__ void __launch_bounds__(256) k_add_drop_ln_bwd(
   }
 }
 
-// dgamma / dbeta = fixed-order sums of the per-block partials: block = 64 columns x 16
-// partial lanes (thread (c, r) takes blocks r, r+16, ...), lanes added in order via LDS;
-// grid (columns / 64, 2): y = 0 gamma, 1 beta
+// dgamma / dbeta = fixed-order sums of the per-block partials (ln_param_grads_block, pgrad.h,
+// shared with the deferred batched launch); grid (columns / 64, 2): y = 0 gamma, 1 beta
 __global__ void __launch_bounds__(1024) k_ln_param_grads(const float *__restrict__ part, int nblk,
                                                          int E, float *__restrict__ dgamma,
                                                          float *__restrict__ dbeta) {
   __shared__ float red[16][64];
-  const int o = threadIdx.x & 63, r = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + o;
-  const float *pp = part + (size_t)blockIdx.y * nblk * E;
-  float s = 0.f;
-  if (c < E)
-    for (int k = r; k < nblk; k += 16) s += pp[(size_t)k * E + c];
-  red[r][o] = s;
-  __syncthreads();
-  if (r == 0 && c < E) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) t += red[j][o];
-    float *out = blockIdx.y == 0 ? dgamma : dbeta;
-    if (out) out[c] = t;
-  }
+  ln_param_grads_block(part, nblk, E, dgamma, dbeta, (int)blockIdx.x, (int)blockIdx.y, red);
 }
 
 }  // namespace e2ep
@@ -205,7 +191,8 @@ static int add_drop_ln_bwd(const float *dy, const float *x, const float *mean, c
   E2EP_REQUIRE(!(dgamma || dbeta) || workspace, E2EP_EINVAL, "e2ep_add_drop_ln_bwd: workspace needed");
   hipLaunchKernelGGL(k_add_drop_ln_bwd, dim3(nblk), dim3(256), 0, stream, dy, x, mean, rstd,
                      gamma, u, seed, p, scale, rows, E, da, db, part);
-  if (part)
+  // inside a deferral scope (pgrad.h) the partial sum waits for e2ep_defer_flush
+  if (part && !pgrad_defer(LnRec{part, dgamma, dbeta, nblk, E}))
     hipLaunchKernelGGL(k_ln_param_grads, dim3(cdiv(E, 64), 2), dim3(1024), 0, stream, part, nblk,
                        E, dgamma, dbeta);
   return launch_status("e2ep_add_drop_ln_bwd");

@@ -8,6 +8,7 @@
 // dx = dy * sigmoid(a) + dpooled / HW in a single stream — no separate avg-pool backward and
 // no autograd add of the two input-gradient paths.
 #include "common.h"
+#include "pgrad.h"
 
 // Contraction only within one expression (a*b + c -> fma): the fp32 and bf16-storage
 // instantiations of a kernel (E2EP_IO_*) then fuse the same operations and round alike —
@@ -373,9 +374,8 @@ __global__ void __launch_bounds__(256) k_se_dpooled(const float *__restrict__ dh
   }
 }
 
-// weight gradients, sums over the batch in sample order (one thread per output):
-//   dW1[k][c] = sum_n dhpre[n][k] pooled[n][c]     dW2[c][k] = sum_n da[n][c] swish(hpre[n][k])
-//   db1[k]    = sum_n dhpre[n][k]                  db2[c]    = sum_n da[n][c]
+// weight gradients, sums over the batch in sample order (one thread per output:
+// se_wgrad_thread, pgrad.h, shared with the deferred batched launch)
 __global__ void __launch_bounds__(256) k_se_wgrad(const float *__restrict__ pooled,
                                                   const float *__restrict__ hpre,
                                                   const float *__restrict__ da,
@@ -383,33 +383,8 @@ __global__ void __launch_bounds__(256) k_se_wgrad(const float *__restrict__ pool
                                                   int sq, float *__restrict__ dw1,
                                                   float *__restrict__ db1, float *__restrict__ dw2,
                                                   float *__restrict__ db2) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n1 = sq * C, n2 = C * sq;
-  float s = 0.f;
-  if (i < n1) {
-    const int k = i / C, c = i - k * C;
-#pragma unroll 8
-    for (int n = 0; n < N; ++n) s += dhpre[(size_t)n * sq + k] * pooled[(size_t)n * C + c];
-    if (dw1) dw1[i] = s;
-  } else if (i < n1 + n2) {
-    const int j = i - n1, c = j / sq, k = j - c * sq;
-#pragma unroll 8
-    for (int n = 0; n < N; ++n) {
-      const float z = hpre[(size_t)n * sq + k];
-      s += da[(size_t)n * C + c] * (z * sigm(z));
-    }
-    if (dw2) dw2[j] = s;
-  } else if (i < n1 + n2 + sq) {
-    const int k = i - n1 - n2;
-#pragma unroll 8
-    for (int n = 0; n < N; ++n) s += dhpre[(size_t)n * sq + k];
-    if (db1) db1[k] = s;
-  } else if (i < n1 + n2 + sq + C) {
-    const int c = i - n1 - n2 - sq;
-#pragma unroll 8
-    for (int n = 0; n < N; ++n) s += da[(size_t)n * C + c];
-    if (db2) db2[c] = s;
-  }
+  se_wgrad_thread(pooled, hpre, da, dhpre, N, C, sq, dw1, db1, dw2, db2,
+                  (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
 // dx = dy * sigmoid(a[plane]) + dpooled[plane] / HW
@@ -560,7 +535,10 @@ static int se_bwd_impl(const void *x, int io, const float *x_scale, const float 
   hipLaunchKernelGGL(k_se_dh, dim3(N, spans), dim3(256), 0, s, da, w2, C, sq, KT, dhp);
   hipLaunchKernelGGL(k_se_dpooled, dim3(N, cdiv(C, 256)), dim3(256), 0, s, dhp, spans, hpre, w1,
                      C, sq, dhpre, dpooled);
-  if (dw1 || db1 || dw2 || db2) {
+  // inside a deferral scope (pgrad.h) the weight gradients wait for e2ep_defer_flush: the
+  // caller keeps pooled, hpre and the workspace (da, dhpre) until then
+  if ((dw1 || db1 || dw2 || db2) &&
+      !pgrad_defer(SeRec{pooled, hpre, da, dhpre, dw1, db1, dw2, db2, N, C, sq})) {
     const int outs = 2 * sq * C + sq + C;
     hipLaunchKernelGGL(k_se_wgrad, dim3(cdiv(outs, 256)), dim3(256), 0, s, pooled, hpre, da, dhpre,
                        N, C, sq, dw1, db1, dw2, db2);

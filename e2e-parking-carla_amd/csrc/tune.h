@@ -40,7 +40,8 @@ enum Tune {
   TUNE_SE_EXCITE_MLP = 34,    // squeeze-excitation logits inside the excite launch: 2 = on, 1 = k_se_logits + k_se_excite
   TUNE_STEM_DIRECT = 35,      // BEV stem (7x7/2, 64 out, 16-bit operands) on the direct-conv kernels: 1 + mask (1 forward k_conv_stem_lp, 2 data gradient k_conv_stem_dgrad_lp, 4 weight gradient k_conv_stem_wgrad_lp; fp32 operands also 8 the gradients, 16 the forward); 1 = the implicit GEMMs
   TUNE_MBCONV_MID = 36,      // MBConv middle on 16x16 maps (_bn0, depthwise, _bn1, SE squeeze) as one launch per direction (mbconv_mid.hip): 2 = on, 1 = the separate launches
-  TUNE_N = 37
+  TUNE_PGRAD_DEFER = 37,     // parameter-gradient finishing launches (split-slab sum, LayerNorm dgamma / dbeta, SE weight gradient) inside a deferral scope (pgrad.h): 2 = recorded and run batched by e2ep_defer_flush, 1 = launched immediately, 3 = only the conv slab sums deferred (benchmarking)
+  TUNE_N = 38
 };
 extern int g_tune[TUNE_N];
 }  // namespace e2ep

@@ -153,6 +153,11 @@ SIGNATURES = {
     "e2ep_bn_small": (_i, [_i]),
     "e2ep_bn_small_limits": (_i, [_i, _i]),
     "e2ep_tune": (_i, [_i, _i]),
+    "e2ep_defer_begin": (_i, []),
+    "e2ep_defer_flush": (_i, [_p]),
+    "e2ep_defer_abort": (_i, []),
+    "e2ep_defer_pending": (_i, []),
+    "e2ep_defer_hold": (_i, [_i]),
     "e2ep_gemm": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "e2ep_gemm_rowsum_workspace": (_sz, [_i, _i, _i]),
     "e2ep_gemm_rowsum": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p, _sz, _p]),

@@ -9,7 +9,7 @@ tensor — the lift-splat backward reads it without a transpose — and the weig
 with the split-K kernel."""
 import torch
 
-from . import _lib, conv, timing
+from . import _lib, conv, defer, timing
 
 
 class _BevStem(torch.autograd.Function):
@@ -36,6 +36,7 @@ class _BevStem(torch.autograd.Function):
                           torch.empty(B, Cout, P, Q, dtype=torch.float32, device=bev.device), w_layout=1)
         ctx.save_for_backward(x, w, wt)
         ctx.meta = (B, C, X, Y, H, W, sh, sw, dims)
+        ctx.pkeys = defer.note(w)  # one more use of w in this forward (defer.py)
         return y
 
     @staticmethod
@@ -54,7 +55,7 @@ class _BevStem(torch.autograd.Function):
             fork = conv._Fork(gy.device, on=ctx.needs_input_grad[0],
                               work_us=conv.est_us(conv.conv_flops(dims)))
             with fork:
-                conv.conv_wgrad(gy, x, dims, dw, ws)
+                conv.conv_wgrad(gy, x, dims, dw, ws, ctx.pkeys)
         if ctx.needs_input_grad[0]:
             dres = conv.conv_dgrad(gy, wt, dims, C,
                                    torch.empty(B, C, H, W, dtype=torch.float32, device=gy.device), w_layout=1)

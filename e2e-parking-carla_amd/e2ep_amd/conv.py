@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from . import _lib, streams, timing
+from . import _lib, defer, streams, timing
 
 
 def _ws(nbytes, device):
@@ -171,12 +171,16 @@ def conv_dgrad(gy, w, dims, m_channels, dx, w_layout=0, res=None):
     return dx
 
 
-def conv_wgrad(gy, x, dims, dw, ws=None):
+def conv_wgrad(gy, x, dims, dw, ws=None, pkeys=defer.ANY):
+    """dw = weight gradient.  Inside a defer.ParamGradDefer scope the slab sum that finishes dw
+    waits for the scope's flush (pkeys: defer.note()'s keys of the weight when autograd owns
+    dw; a direct caller must not read dw before the flush)."""
     d = _lib.dims(dims)
     splits = _lib.load().e2ep_conv_wgrad_splits(d)
     if ws is None:
         ws = torch.empty(splits * dw.numel(), dtype=torch.float32, device=gy.device)
-    with timing.region(_rname("conv_wgrad", dims), conv_flops(dims)):
+    with timing.region(_rname("conv_wgrad", dims), conv_flops(dims)), defer.call(pkeys) as dc:
+        dc.keep(ws)  # the slabs, read by the deferred sum
         _lib.call("e2ep_conv_wgrad", _lib.ptr(gy), _lib.ptr(x), d, splits, _lib.ptr(ws), _lib.nbytes(ws),
                   _lib.ptr(dw), 0, _lib.stream(), _io_x(x))
     return dw
@@ -302,7 +306,7 @@ def set_conv_pair(on):
     return prev
 
 
-def _conv_bwd_pair(gy, x, wt, dims, gc, gskip, wshape):
+def _conv_bwd_pair(gy, x, wt, dims, gc, gskip, wshape, pkeys=None):
     """(dx, dw) of a conv through e2ep_conv_bwd; dx as _Conv2d.backward's dgrad path builds it."""
     N, Cin, H, W = dims[:4]
     lib = _lib.load()
@@ -313,7 +317,9 @@ def _conv_bwd_pair(gy, x, wt, dims, gc, gskip, wshape):
     wsd = _ws(lib.e2ep_conv_dgrad_workspace(d, gc), gy.device)
     res = gskip.contiguous() if (gskip is not None and gc == Cin) else None
     dxg = torch.empty(N, gc, H, W, dtype=x.dtype, device=x.device)  # bf16 for a bf16-stored x
-    with timing.region(_rname("conv_bwd", dims, f"gc{gc}"), conv_flops(dims, gc) + conv_flops(dims)):
+    with timing.region(_rname("conv_bwd", dims, f"gc{gc}"), conv_flops(dims, gc) + conv_flops(dims)), \
+            defer.call(pkeys) as dc:
+        dc.keep(wsw)  # the weight gradient's slabs, read by the deferred sum
         _lib.call("e2ep_conv_bwd", _lib.ptr(gy), _lib.ptr(x), _lib.ptr(wt), d, gc, _lib.ptr(res),
                   _lib.ptr(dxg), _lib.ptr(wsd), _lib.nbytes(wsd), splits, _lib.ptr(wsw),
                   _lib.nbytes(wsw), _lib.ptr(dw), _lib.stream(), (_IO_X | _IO_DX) if _io_x(x) else 0)
@@ -339,6 +345,7 @@ class _Conv2d(torch.autograd.Function):
         ctx.dims, ctx.act, ctx.has_bias, ctx.gc = dims, act, b is not None, grad_channels
         ctx.save_for_backward(x, wt, y if act else None)
         ctx.wshape = w.shape
+        ctx.pkeys = defer.note(w)  # one more use of w in this forward (defer.py)
         ctx.skip = skip
         # an unused skip alias (a trunk endpoint nobody reads) arrives as None, not as a
         # zero-filled gradient
@@ -367,7 +374,7 @@ class _Conv2d(torch.autograd.Function):
         xb = x.dtype == torch.bfloat16
         if want_w and ctx.needs_input_grad[0] and _CONV_PAIR[0] and (not xb or gskip is None) and \
                 _lib.load().e2ep_conv_bwd_pair_ok(_lib.dims(dims), gc):
-            dx, dw = _conv_bwd_pair(gy, x, wt, dims, gc, gskip, ctx.wshape)
+            dx, dw = _conv_bwd_pair(gy, x, wt, dims, gc, gskip, ctx.wshape, ctx.pkeys)
             if want_b:
                 db = torch.empty(Cout, dtype=torch.float32, device=x.device)
                 _lib.call("e2ep_bias_grad", _lib.ptr(gy), N, Cout, P * Q, _lib.ptr(db), s)
@@ -383,7 +390,7 @@ class _Conv2d(torch.autograd.Function):
             fork = _Fork(x.device, on=ctx.needs_input_grad[0], work_us=est_us(conv_flops(dims)))
             with fork:
                 if want_w:
-                    conv_wgrad(gy, x, dims, dw, ws)
+                    conv_wgrad(gy, x, dims, dw, ws, ctx.pkeys)
                 if want_b:
                     _lib.call("e2ep_bias_grad", _lib.ptr(gy), N, Cout, P * Q, _lib.ptr(db),
                               _lib.stream())
@@ -425,6 +432,7 @@ class _Linear1x1(torch.autograd.Function):
         _skinny(x2, K, 1, w2, 1, K, b, N, M, K, y)
         ctx.save_for_backward(x2, w2)
         ctx.has_bias, ctx.wshape, ctx.xshape = b is not None, w.shape, x.shape
+        defer.note(w)  # a use of w (nothing of this backward defers; a conv sharing w must not)
         return y.view(N, M, 1, 1)
 
     @staticmethod

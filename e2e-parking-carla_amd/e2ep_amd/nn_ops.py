@@ -7,7 +7,7 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import _lib, conv, rng, timing
+from . import _lib, conv, defer, rng, timing
 
 ACT = {None: 0, "none": 0, "relu": 1, "swish": 2}
 
@@ -689,6 +689,7 @@ class _SqueezeExcite(torch.autograd.Function):
                       _lib.ptr(y), _lib.stream(), 0)
         ctx.save_for_backward(x, w1c, w2c, pooled, hpre, a)
         ctx.shapes = (w1.shape, w2.shape, b1 is not None, b2 is not None)
+        ctx.pkeys = defer.note(w1, b1, w2, b2)
         return y
 
     @staticmethod
@@ -705,7 +706,9 @@ class _SqueezeExcite(torch.autograd.Function):
         dw2 = torch.empty(w2s, dtype=torch.float32, device=dev) if nig[3] else None
         db2 = torch.empty(C, dtype=torch.float32, device=dev) if (hb2 and nig[4]) else None
         ws = torch.empty(2 * N * C + 17 * N * sq, dtype=torch.float32, device=dev)
-        with timing.region(timing.name("se_bwd", x.shape, "_SqueezeExcite")):
+        with timing.region(timing.name("se_bwd", x.shape, "_SqueezeExcite")), \
+                defer.call(ctx.pkeys) as dc:
+            dc.keep(pooled, hpre, ws)  # read by the deferred weight gradients (da, dhpre in ws)
             _lib.call("e2ep_se_bwd", _lib.ptr(x), None, None, _lib.ptr(dy.contiguous()),
                       _lib.ptr(w1c), _lib.ptr(w2c), _lib.ptr(pooled), _lib.ptr(hpre), _lib.ptr(a),
                       N, C, H * W, sq, _lib.ptr(dx), None, _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2),
@@ -771,6 +774,7 @@ class _BnSwishSE(torch.autograd.Function):
                       (_IO_X | (_IO_DX if yb else 0)) if hb else 0)
         ctx.save_for_backward(x, gamma, beta, stats, w1c, w2c, pooled, hpre, a)
         ctx.shapes = (w1.shape, w2.shape, b1 is not None, b2 is not None)
+        ctx.pkeys = defer.note(w1, b1, w2, b2)
         ctx.train = train
         return y
 
@@ -803,7 +807,9 @@ class _BnSwishSE(torch.autograd.Function):
                  and _lib.load().e2ep_bn_bwd_split(N, C, H, W) == 1)
         if fused:
             planes = torch.empty(N * C * 4, dtype=torch.float64, device=dev)
-            with timing.region(timing.name("se_bwd", x.shape, "_BnSwishSE")):
+            with timing.region(timing.name("se_bwd", x.shape, "_BnSwishSE")), \
+                    defer.call(ctx.pkeys) as dc:
+                dc.keep(pooled, hpre, ws)  # read by the deferred weight gradients
                 _lib.call("e2ep_se_bwd_bn", _lib.ptr(x), _lib.ptr(stats[2]), _lib.ptr(stats[3]),
                           _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(gamma), _lib.ptr(beta),
                           _lib.ptr(dy), _lib.ptr(w1c), _lib.ptr(w2c), _lib.ptr(pooled),
@@ -816,7 +822,9 @@ class _BnSwishSE(torch.autograd.Function):
                           _lib.ptr(dpooled), _lib.ptr(planes), N, C, H, W, ACT["swish"],
                           _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), s, (io_in | _IO_DX) if hb else 0)
             return dx, dg, db, None, None, None, None, None, dw1, db1, dw2, db2, None, None, None
-        with timing.region(timing.name("se_bwd", x.shape, "_BnSwishSE")):
+        with timing.region(timing.name("se_bwd", x.shape, "_BnSwishSE")), \
+                defer.call(ctx.pkeys) as dc:
+            dc.keep(pooled, hpre, ws)  # read by the deferred weight gradients
             _lib.call("e2ep_se_bwd", _lib.ptr(x), _lib.ptr(stats[2]), _lib.ptr(stats[3]),
                       _lib.ptr(dy), _lib.ptr(w1c), _lib.ptr(w2c), _lib.ptr(pooled),
                       _lib.ptr(hpre), _lib.ptr(a), N, C, H * W, sq, None, _lib.ptr(dpooled),
@@ -902,6 +910,7 @@ class _MBConvMid(torch.autograd.Function):
         ctx.save_for_backward(x, y1, w, g0, b0, st0, g1, b1, st1, w1c, w2c, pooled, hpre, a)
         ctx.dims = dims
         ctx.shapes = (w1.shape, w2.shape, sb1 is not None, sb2 is not None)
+        ctx.pkeys = defer.note(w1, sb1, w2, sb2)
         return y
 
     @staticmethod
@@ -920,7 +929,9 @@ class _MBConvMid(torch.autograd.Function):
         dsb2 = torch.empty(C, **f32) if (hb2 and nig[18]) else None
         dpooled = torch.empty(N, C, **f32)
         ws = torch.empty(2 * N * C + 17 * N * sq, **f32)
-        with timing.region(timing.name("se_bwd", x.shape, "_MBConvMid")):
+        with timing.region(timing.name("se_bwd", x.shape, "_MBConvMid")), \
+                defer.call(ctx.pkeys) as dc:
+            dc.keep(pooled, hpre, ws)  # read by the deferred weight gradients
             _lib.call("e2ep_se_bwd", _lib.ptr(y1), _lib.ptr(st1[2]), _lib.ptr(st1[3]), _lib.ptr(dy),
                       _lib.ptr(w1c), _lib.ptr(w2c), _lib.ptr(pooled), _lib.ptr(hpre), _lib.ptr(a),
                       N, C, 256, sq, None, _lib.ptr(dpooled), _lib.ptr(dw1), _lib.ptr(dsb1),
@@ -1103,6 +1114,7 @@ class _AddDropLN(torch.autograd.Function):
                       _lib.ptr(mean), _lib.ptr(rstd), _lib.stream())
         ctx.save_for_backward(x, mean, rstd, gamma, mask)
         ctx.p, ctx.rows, ctx.E, ctx.seeded = float(p), rows, E, seed is not None
+        ctx.pkeys = defer.note(gamma, beta)
         return y
 
     @staticmethod
@@ -1114,7 +1126,9 @@ class _AddDropLN(torch.autograd.Function):
         dg = torch.empty_like(gamma) if (gamma is not None and nig[2]) else None
         dbeta = torch.empty_like(gamma) if (gamma is not None and nig[3]) else None
         ws = _ws(_lib.load().e2ep_add_drop_ln_bwd_workspace(ctx.rows, ctx.E), x.device)
-        with timing.region(timing.name("ln_bwd", x.shape, "_AddDropLN")):
+        with timing.region(timing.name("ln_bwd", x.shape, "_AddDropLN")), \
+                defer.call(ctx.pkeys) as dc:
+            dc.keep(ws)  # the dgamma / dbeta partials, read by the deferred sum
             _lib.call("e2ep_add_drop_ln_bwd_seeded" if ctx.seeded else "e2ep_add_drop_ln_bwd",
                       _lib.ptr(dy.contiguous()), _lib.ptr(x), _lib.ptr(mean),
                       _lib.ptr(rstd), _lib.ptr(gamma), _lib.ptr(mask), ctx.p, ctx.rows, ctx.E,

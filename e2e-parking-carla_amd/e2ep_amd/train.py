@@ -66,7 +66,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import _lib, graphs, segments
+from . import _lib, defer, graphs, segments
 from .optim import FlatAdam
 
 BUCKET_MB = 25.0  # DistributedDataParallel's default bucket_cap_mb
@@ -295,14 +295,23 @@ class TrainStep:
     def _fwd_bwd(self):
         self.opt.zero_grad(set_to_none=True)  # autograd hands its gradient tensors over
         if self.buckets is not None:
+            # the gradient hooks read .grad during the backward: every parameter gradient is
+            # finished where it is produced (no deferral scope)
             self.buckets.arm()
+            loss = self._loss_backward()
+            self.buckets.finish()
+            return loss
+        # parameter-gradient finishing launches run batched at the scope's exit (defer.py):
+        # nothing reads a .grad before the gather / optimizer that follows
+        with defer.ParamGradDefer():
+            return self._loss_backward()
+
+    def _loss_backward(self):
         loss = self.module.training_step(self.batch, 0)
         # the seed gradient: a persistent ones scalar (loss.backward() would fill one per step)
         if getattr(self, "_one", None) is None or self._one.device != loss.device:
             self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
         loss.backward(self._one)
-        if self.buckets is not None:
-            self.buckets.finish()
         return loss.detach()
 
     def _gather(self):
@@ -359,14 +368,19 @@ class TrainStep:
     # -- segmented backward (graph mode with RCCL) ----------------------------------------
     def _stage1(self):
         self.opt.zero_grad(set_to_none=True)
-        with segments.record() as rec:
-            loss = self.module.training_step(self.batch, 0)
-        self._pairs = rec.pairs
-        loss.backward()
+        # one deferral scope per stage (defer.py), so that a stage's gradients are complete
+        # before its gather; stage 2 continues with the forward's use counts
+        with defer.ParamGradDefer() as scope:
+            with segments.record() as rec:
+                loss = self.module.training_step(self.batch, 0)
+            self._pairs = rec.pairs
+            loss.backward()
+        self._defer_uses = scope.uses
         return loss.detach()
 
     def _stage2(self):
-        segments.backward_rest(self._pairs)
+        with defer.ParamGradDefer(uses=self._defer_uses):
+            segments.backward_rest(self._pairs)
 
     def _buckets_of(self, i0, i1, bucket_mb):
         """Flat ranges of ~bucket_mb over parameters [i0, i1), last parameters first (the

@@ -873,7 +873,9 @@ int e2ep_bn_small_limits(int fwd_max_vec, int bwd_max_vec);
  * 26 the same for channels of 257..1024 float4 (2 = 512 threads; 1 = 256, default: equal),
  * 28 split-K reductions folded into the producing launch (2, default) or separate reduce
  * kernels (1), 30 1x1 paired backward block order (2 = weight-gradient blocks first, default;
- * 1 = data-gradient first).  Keys 27, 29 and 31 are retired (their A/B kept the default and the
+ * 1 = data-gradient first), 37 parameter-gradient finishing launches inside a deferral scope
+ * (e2ep_defer_begin below: 2 = deferred, default; 1 = launched immediately; 3 = only the conv
+ * slab sums deferred).  Keys 27, 29 and 31 are retired (their A/B kept the default and the
  * alternative code is removed): they return -1 like an unknown key.
  * For A/B timing.
  * Contract for every plan override and tunable above (e2ep_conv_split_params,
@@ -886,6 +888,33 @@ int e2ep_bn_small_limits(int fwd_max_vec, int bwd_max_vec);
  * would run needs more (round 4: a plan changed after the query can no longer write past the
  * buffer). */
 int e2ep_tune(int key, int value);
+
+/* Deferred parameter-gradient finishing (csrc/pgrad.hip; additions within ABI 4).
+ * Three launches of a backward produce parameter gradients only, which nothing reads before
+ * the optimizer or the gradient gather: the split-slab sum that ends e2ep_conv_wgrad and
+ * e2ep_conv_bwd, the dgamma / dbeta partial sum of e2ep_add_drop_ln_bwd*, and the weight
+ * gradients of e2ep_se_bwd*.  Between e2ep_defer_begin and e2ep_defer_flush (with e2ep_tune key
+ * 37 = 2) those entry points record that launch's arguments instead of issuing it, and the
+ * flush runs one batched kernel per kind on `stream` (again with the remainder when more
+ * records are pending than one launch's arguments hold), in record order within a kind.  Every
+ * output is summed in the same order as by the immediate launch: equal bit for bit.
+ * The state is process-global (one scope at a time, any thread, calls never concurrent).
+ * Until the flush the caller keeps alive, and does not write, what a record reads: the conv
+ * slab workspace, the LayerNorm workspace, the SE `pooled`, `hpre` and workspace; and it must
+ * not read the deferred outputs (dw; dgamma, dbeta; dw1, db1, dw2, db2).  Two LayerNorm or SE
+ * records of one output must not share a scope (use e2ep_defer_hold for a parameter used twice).
+ * The flush must be ordered after every recording call's stream work (same stream, or joined).
+ * e2ep_defer_begin: E2EP_EINVAL when a scope is open.  e2ep_defer_flush: launches, clears the
+ * list and closes the scope (E2EP_EINVAL without one).  e2ep_defer_abort: clears and closes,
+ * launching nothing.  e2ep_defer_pending: the number of pending records.  e2ep_defer_hold(1):
+ * calls launch immediately although a scope is open, until e2ep_defer_hold(0); returns the
+ * previous setting; begin, flush and abort reset it. */
+int e2ep_defer_begin(void);
+int e2ep_defer_flush(void *stream);
+int e2ep_defer_abort(void);
+int e2ep_defer_pending(void);
+int e2ep_defer_hold(int hold);
+
 int e2ep_gemm(const float *A, int lda, int a_kcontig, const float *B, int ldb, int b_kcontig,
               const float *bias, const float *Cadd, int ldadd, float *C, int ldc, int M, int N,
               int K, int relu, void *workspace, size_t workspace_bytes, void *stream);
