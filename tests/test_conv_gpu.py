@@ -510,16 +510,10 @@ def _plan_ref(name):
     return ref
 
 
-@pytest.mark.parametrize("setting", list(PLAN_SETTINGS))
-@pytest.mark.parametrize("shape", list(PLAN_SHAPES))
-def test_conv_queries_agree_with_launches(shape, setting):
-    """Forward, data gradient, weight gradient and (where e2ep_conv_bwd_pair_ok) the paired
-    backward through the C ABI, every workspace of exactly the queried size and the statistics
-    buffer of exactly Cout x tiles x 2 doubles: every call returns 0, the results stay within
-    the fp64 bounds of test_conv_fwd_bwd_vs_fp64 (fp32: 2e-6) and
-    test_conv_low_precision_operands (bf16, against rounded operands: 2e-6, weight gradient
-    5e-6), and the paired results are bitwise the two launches'."""
-    import ctypes
+def plan_launches(shape, setting):
+    """test_conv_queries_agree_with_launches' call sequence through the C ABI (every workspace
+    of exactly the queried size); returns its outputs, for that test's assertions and for the
+    guarded runs of test_guarded_ops_gpu.py."""
     from e2ep_amd import _lib, precision
     lib = _lib.load()
     N, Cin, H, W, Cout, K, st, pad, dil, gc = PLAN_SHAPES[shape]
@@ -572,6 +566,27 @@ def test_conv_queries_agree_with_launches(shape, setting):
     finally:
         for k, v in old.items():
             lib.e2ep_tune(k, v)
+    return {"y": y, "dx": dx, "dw": dw, "stats": stats, "pair": pair, "tiles": tiles, "splits": splits}
+
+
+@pytest.mark.parametrize("setting", list(PLAN_SETTINGS))
+@pytest.mark.parametrize("shape", list(PLAN_SHAPES))
+def test_conv_queries_agree_with_launches(shape, setting):
+    """Forward, data gradient, weight gradient and (where e2ep_conv_bwd_pair_ok) the paired
+    backward through the C ABI, every workspace of exactly the queried size and the statistics
+    buffer of exactly Cout x tiles x 2 doubles: every call returns 0, the results stay within
+    the fp64 bounds of test_conv_fwd_bwd_vs_fp64 (fp32: 2e-6) and
+    test_conv_low_precision_operands (bf16, against rounded operands: 2e-6, weight gradient
+    5e-6), and the paired results are bitwise the two launches'."""
+    check_plan_launches(shape, setting, plan_launches(shape, setting))
+
+
+def check_plan_launches(shape, setting, out):
+    Cout = PLAN_SHAPES[shape][4]
+    mode = PLAN_SETTINGS[setting][0]
+    ref = _plan_ref(shape)
+    y, dx, dw, stats, pair, tiles, splits = (out[k] for k in ("y", "dx", "dw", "stats", "pair", "tiles",
+                                                              "splits"))
     y64, dx64, dw64 = ref[mode]
     # the direct kernel (tiny Cin x R x S) multiplies fp32 operands in every mode
     fwd_ref = ref["fp32"][0] if shape == "direct" else y64
