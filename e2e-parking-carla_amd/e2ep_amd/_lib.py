@@ -6,179 +6,90 @@ silently degrades to PyTorch or CPU code.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (loads torch's libamdhip64 first, so the library binds to it)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E2EP_LIB", os.path.join(_HERE, "libe2ep_hip.so"))
 
-_p, _i, _i64, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t
-_d = ctypes.c_double
-_fp3 = ctypes.POINTER(ctypes.c_float)
+HEADER_PATH = os.environ.get("E2EP_HEADER", os.path.join(_HERE, "..", "..", "include", "e2ep.h"))
 
-# name -> (restype, argtypes); must match include/e2ep.h
-SIGNATURES = {
-    "e2ep_abi_version": (_i, []),
-    "e2ep_last_error": (ctypes.c_char_p, []),
-    "e2ep_rig_transforms": (_i, [_p, _p, _i, _p, _p, _p]),
-    "e2ep_geom_index": (_i, [_p, _p, _p, _fp3, _fp3, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
-    "e2ep_lss_plan_workspace": (_sz, [_i, _i]),
-    "e2ep_lss_tiles": (_i, [_i]),
-    "e2ep_debug_fwd_trace": (_i, [_p]),
-    "e2ep_lss_plan": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
-    "e2ep_lss_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i64, _p]),
-    "e2ep_lss_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "e2ep_transpose": (_i, [_p, _i64, _i, _i, _i, _p, _p]),
-    "e2ep_transpose_multi": (_i, [_p, _i, _i, _p]),
-    "e2ep_target_bev": (_i, [_p, _p, _i, _i, _i, _f, _f, _p, _i64, _p]),
-    "e2ep_conv_fwd_workspace": (_sz, [_p]),
-    "e2ep_conv_fwd": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _sz, _p, _i]),
-    "e2ep_conv_fwd_stats_tiles": (_i, [_p, _i]),
-    "e2ep_conv_fwd_stats": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _sz, _p, _sz, _p, _i]),
-    "e2ep_conv_dgrad_workspace": (_sz, [_p, _i]),
-    "e2ep_conv_dgrad": (_i, [_p, _p, _p, _i, _i, _p, _p, _sz, _p]),
-    "e2ep_conv_dgrad_acc": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _sz, _p, _i]),
-    "e2ep_conv_gemm_variant": (_i, [_i]),
-    "e2ep_conv_split_params": (_i, [_i, _i, _i]),
-    "e2ep_conv_precision": (_i, [_i]),
-    "e2ep_gemm_precision": (_i, [_i]),
-    "e2ep_fusion_tokens_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p]),
-    "e2ep_fusion_tokens_bwd": (_i, [_p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
-    "e2ep_embed_tokens_fwd": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _f, _p, _p, _p]),
-    "e2ep_embed_tokens_bwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
-    "e2ep_conv_wgrad_kstep": (_i, [_i]),
-    "e2ep_conv_wgrad_splits": (_i, [_p]),
-    "e2ep_conv_wgrad_workspace": (_sz, [_p, _i]),
-    "e2ep_conv_wgrad": (_i, [_p, _p, _p, _i, _p, _sz, _p, _i, _p, _i]),
-    "e2ep_conv_bwd_pair_ok": (_i, [_p, _i]),
-    "e2ep_conv_bwd": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _sz, _i, _p, _sz, _p, _p, _i]),
-    "e2ep_bias_grad": (_i, [_p, _i, _i, _i, _p, _p]),
-    "e2ep_col_sum_workspace": (_sz, [_i, _i]),
-    "e2ep_col_sum": (_i, [_p, _i, _i, _p, _p, _p]),
-    "e2ep_skinny_gemm": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _p, _p]),
-    "e2ep_bn_workspace": (_sz, [_i, _i, _i, _i]),
-    "e2ep_bn_fwd": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _sz, _p]),
-    "e2ep_bn_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _sz, _p, _i]),
-    "e2ep_bn_fwd_split": (_i, [_i, _i, _i, _i]),
-    "e2ep_bn_finalize_part_workspace": (_sz, [_i, _i]),
-    "e2ep_bn_finalize_part": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _sz, _p]),
-    "e2ep_bn_apply": (_i, [_p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _p, _p]),
-    "e2ep_bn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p, _i]),
-    "e2ep_act_fwd": (_i, [_p, _i64, _i, _p, _p]),
-    "e2ep_act_bwd": (_i, [_p, _p, _i64, _i, _p, _p]),
-    "e2ep_cat_channels": (_i, [_p, _p, _i, _i, _i64, _p, _p]),
-    "e2ep_split_channels": (_i, [_p, _p, _i, _i, _i64, _p, _p]),
-    "e2ep_sum3": (_i, [_p, _p, _p, _p, _p]),
-    "e2ep_add_f32": (_i, [_p, _p, _i64, _p, _p]),
-    "e2ep_rng_draw": (_i, [_p, _i, _p, _i, _p, _p]),
-    "e2ep_eq_mask_i64": (_i, [_p, _i64, _i, _i, _i64, _p, _p]),
-    "e2ep_add_i64_multi": (_i, [_p, _i, _i64, _p]),
-    "e2ep_resize_fwd": (_i, [_p, _i, _i, _i64, _i, _i, _i, _i, _f, _f, _p, _i64, _p]),
-    "e2ep_resize_bwd_workspace": (_sz, [_i, _i, _i]),
-    "e2ep_resize_bwd": (_i, [_p, _i64, _i, _i, _i, _i, _i, _f, _f, _p, _i, _p, _p]),
-    "e2ep_resize_bwd_cl": (_i, [_p, _i64, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p]),
-    "e2ep_dwconv_fwd": (_i, [_p, _p, _p, _p, _p, _i, _p, _p]),
-    "e2ep_dwconv_fwd_stats_tiles": (_i, [_p]),
-    "e2ep_dwconv_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _sz, _p, _i]),
-    "e2ep_dwconv_dgrad": (_i, [_p, _p, _p, _p, _p, _i]),
-    "e2ep_dwconv_wgrad_workspace": (_sz, [_p]),
-    "e2ep_dwconv_wgrad": (_i, [_p, _p, _p, _p, _p, _i, _p, _sz, _p, _p, _i]),
-    "e2ep_dwconv_bwd_pair_ok": (_i, [_p]),
-    "e2ep_dwconv_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _sz, _p, _p, _i]),
-    "e2ep_maxpool3s2_fwd": (_i, [_p, _i, _i, _i, _p, _p, _p]),
-    "e2ep_maxpool3s2_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p]),
-    "e2ep_avgpool_fwd": (_i, [_p, _i, _i, _p, _p]),
-    "e2ep_avgpool_bwd": (_i, [_p, _i, _i, _p, _p]),
-    "e2ep_add_drop_ln_fwd": (_i, [_p, _p, _p, _f, _p, _p, _i, _i, _f, _p, _p, _p, _p, _p]),
-    "e2ep_add_drop_ln_bwd_workspace": (_sz, [_i, _i]),
-    "e2ep_add_drop_ln_fwd_seeded": (_i, [_p, _p, _p, _f, _p, _p, _i, _i, _f, _p, _p, _p, _p, _p]),
-    "e2ep_add_drop_ln_bwd_seeded": (_i, [_p, _p, _p, _p, _p, _p, _f, _i, _i, _p, _p, _p, _p, _p, _p]),
-    "e2ep_add_drop_ln_bwd": (_i, [_p, _p, _p, _p, _p, _p, _f, _i, _i, _p, _p, _p, _p, _p, _p]),
-    "e2ep_attn_fwd": (_i, [_p, _p, _p] + [_i] * 11 + [_f, _i, _p, _f, _p, _p, _p, _p]),
-    "e2ep_attn_weights": (_i, [_p, _p, _p] + [_i] * 9 + [_f, _i, _p, _i, _p, _p]),
-    "e2ep_attn_bwd_workspace": (_sz, [_i, _i, _i]),
-    "e2ep_attn_bwd": (_i, [_p] * 6 + [_i] * 11 + [_f, _i, _p, _f, _p, _p, _p, _p, _p, _p]),
-    "e2ep_attn_bwd_part": (_i, [_p] * 6 + [_i] * 11 + [_f, _i, _p, _f, _p, _p, _p, _p, _p, _i, _p]),
-    "e2ep_attn_keep_mask": (_i, [_p, _i, _i, _i, _f, _p, _p]),
-    "e2ep_softmax_c_fwd": (_i, [_p, _i, _i, _i, _p, _p]),
-    "e2ep_softmax_c_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p]),
-    "e2ep_relu_dropout_fwd": (_i, [_p, _i64, _f, _p, _p, _p]),
-    "e2ep_relu_dropout_bwd": (_i, [_p, _p, _i64, _f, _p, _p, _p]),
-    "e2ep_se_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i]),
-    "e2ep_se_fwd_pooled": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i]),
-    "e2ep_mbconv_mid_ok": (_i, [_p]),
-    "e2ep_mbconv_mid_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p]),
-    "e2ep_mbconv_mid_bwd": (_i, [_p] * 20),
-    "e2ep_se_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i]),
-    "e2ep_se_bwd_bn": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i]),
-    "e2ep_bn_bwd_planes": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i]),
-    "e2ep_bn_bwd_split": (_i, [_i, _i, _i, _i]),
-    "e2ep_bn_eval_multi": (_i, [_p, _i, _p]),
-    "e2ep_se_gate_fwd": (_i, [_p, _p, _i, _i, _p, _p]),
-    "e2ep_se_gate_bwd": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
-    "e2ep_adam_chunk_elems": (_i, []),
-    "e2ep_adam_step": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _f, _p, _p]),
-    "e2ep_grad_gather": (_i, [_p, _i, _p, _p, _p, _p]),
-    "e2ep_grad_sqnorm": (_i, [_p, _i, _p, _p, _p, _p, _p]),
-    "e2ep_grad_norm_finalize": (_i, [_p, _i, _f, _d, _i, _p, _p, _p, _p, _p]),
-    "e2ep_adam_step_clipped": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _f,
-                                    _p, _p, _p, _p]),
-    "e2ep_grad_accumulate": (_i, [_p, _i, _p, _p, _p, _p]),
-    "e2ep_graph_replace_memsets": (_i, [_p, ctypes.POINTER(_i)]),
-    "e2ep_graph_exec_create": (_i, [_p, _p]),
-    "e2ep_graph_exec_launch": (_i, [_p, _p]),
-    "e2ep_graph_exec_destroy": (_i, [_p]),
-    "e2ep_capture_unjoined": (_i, [_p, _p, ctypes.POINTER(_i)]),
-    "e2ep_tokens_init": (_i, [_p, _i, _i, _i, _p, _i, _i64, _p]),
-    "e2ep_token_argmax_append": (_i, [_p, _i64, _i, _i, _p, _i, _i, _p]),
-    "e2ep_dec_self_attn": (_i, [_p, _i, _p, _p, _f, _p, _i, _p, _p, _p, _i, _i64, _p, _p, _p, _p,
-                                _i, _i, _i, _i, _i, _p]),
-    "e2ep_dec_cross_attn": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _i, _p, _i, _i, _i, _i, _p]),
-    "e2ep_dec_row_gemv": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _i, _p, _p, _f, _p, _i, _i, _i, _i,
-                               _i, _p]),
-    "e2ep_dwconv_bf16_ok": (_i, [_p]),
-    "e2ep_control_ce_workspace": (_sz, [_i]),
-    "e2ep_control_ce_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    "e2ep_control_ce_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
-    "e2ep_seg_ce_workspace": (_sz, [_i, _i]),
-    "e2ep_seg_ce_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
-    "e2ep_seg_ce_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
-    "e2ep_depth_bce_workspace": (_sz, [_i, _i, _i, _i]),
-    "e2ep_depth_bce_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
-    "e2ep_depth_bce_fwd_f64": (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _d, _p, _p, _p, _p, _p]),
-    "e2ep_gemm_workspace": (_sz, [_i, _i, _i]),
-    "e2ep_gemm_force": (_i, [_i, _i, _i]),
-    "e2ep_gemm_skinny": (_i, [_i]),
-    "e2ep_gemm_split_min": (_i, [_i]),
-    "e2ep_bn_small": (_i, [_i]),
-    "e2ep_bn_small_limits": (_i, [_i, _i]),
-    "e2ep_tune": (_i, [_i, _i]),
-    "e2ep_defer_begin": (_i, []),
-    "e2ep_defer_flush": (_i, [_p]),
-    "e2ep_defer_abort": (_i, []),
-    "e2ep_defer_pending": (_i, []),
-    "e2ep_defer_hold": (_i, [_i]),
-    "e2ep_gemm": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _sz, _p]),
-    "e2ep_gemm_rowsum_workspace": (_sz, [_i, _i, _i]),
-    "e2ep_gemm_rowsum": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p, _sz, _p]),
-    "e2ep_linear_bwd": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p, _sz, _p, _sz, _p]),
-    "e2ep_decode_frames": (_i, [_p, _p, _p, _i64, _i, _p, _p, _p]),
-    "e2ep_widen_u8_i64": (_i, [_p, _p, _i64, _i, _p, _p]),
-    "e2ep_depth_bce_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p]),
-    "e2ep_decode_bgra": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
-    "e2ep_slot_stats_workspace": (_sz, [_i, _i]),
-    "e2ep_slot_partials": (_i, [_p, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
-    "e2ep_slot_finish": (_i, [_p, _sz, _i, _i, _i, _d, _d, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p,
-                              _p]),
-    "e2ep_target_select": (_i, [_p, _p, _i, _p, _p]),
-}
-
-_LIB = None
-_ERR = None
+_POINTER = ctypes.c_void_p  # every pointer argument, host or device, typed or void
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "long long": ctypes.c_longlong,
+            "int64_t": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t}
 
 
 class E2EPError(RuntimeError):
     pass
+
+
+def _ctype(decl, text, ret=False):
+    """ctypes type of one argument (`type name`) or, with ret, of a return type."""
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    if ret and words == ["char", "*"]:
+        return ctypes.c_char_p
+    if "*" in words and not ret:
+        return _POINTER
+    kind = " ".join(words if ret else words[:-1])  # an argument's last word is its name
+    if kind not in _SCALARS:
+        raise E2EPError(f"e2ep.h: cannot map `{text.strip()}` of `{decl}` to ctypes")
+    return _SCALARS[kind]
+
+
+def parse_header(text):
+    """(signatures, constants) of the C ABI from the text of e2ep.h: name -> (restype,
+    argtypes) for every `ret name(args);`, and name -> int for every `#define E2EP_* <int>`.
+    A declaration whose types are not in the table above raises: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts = {m[1]: int(m[2]) for m in re.finditer(
+        r"^[ \t]*#[ \t]*define[ \t]+(E2EP_\w+)[ \t]+\(?[ \t]*(-?\d+)[ \t]*\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    sigs = {}
+    for m in re.finditer(r"([^;{}]+);", text):
+        decl = " ".join(m[1].split())
+        d = re.fullmatch(r"(.+?)(\w+) ?\(([^()]*)\)", decl)
+        if d is None:
+            raise E2EPError(f"e2ep.h: cannot parse `{decl}`")
+        args = [] if d[3].strip() in ("", "void") else d[3].split(",")
+        sigs[d[2]] = (_ctype(decl, d[1], ret=True), [_ctype(decl, a) for a in args])
+    return sigs, consts
+
+
+_HEADER = None
+
+
+def _header():
+    """The parsed header, read once per process on first use (load(), SIGNATURES, CONSTANTS)."""
+    global _HEADER
+    if _HEADER is None:
+        try:
+            with open(HEADER_PATH) as f:
+                text = f.read()
+        except OSError as e:
+            raise E2EPError(f"C ABI header unavailable ({HEADER_PATH}): {e}") from None
+        _HEADER = parse_header(text)
+    return _HEADER
+
+
+def __getattr__(name):
+    if name == "SIGNATURES":  # name -> (restype, argtypes)
+        return _header()[0]
+    if name == "CONSTANTS":  # the header's integer E2EP_* macros
+        return _header()[1]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def io_mask(x=False, dy=False, dx=False):
+    """The `io` argument (E2EP_IO_*): which of a call's tensors are stored bf16."""
+    c = _header()[1]
+    return ((c["E2EP_IO_X_BF16"] if x else 0) | (c["E2EP_IO_DY_BF16"] if dy else 0)
+            | (c["E2EP_IO_DX_BF16"] if dx else 0))
+
+
+_LIB = None
+_ERR = None
 
 
 def load():
@@ -188,9 +99,10 @@ def load():
         return _LIB
     if _ERR is not None:
         raise _ERR
+    signatures = _header()[0]
     try:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in signatures.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     except (OSError, AttributeError) as e:

@@ -125,11 +125,8 @@ def tap_major(w):
 # bf16 activation storage (e2ep.h E2EP_IO_*; nn_ops._store_bf16): a bf16 input of a conv (the
 # MBConv project conv reading the bf16-stored squeeze-excitation output, C3) is read as bf16 by
 # the bf16-operand kernels, and its data gradient is written bf16
-_IO_X, _IO_DX = 1, 4
-
-
 def _io_x(x):
-    return _IO_X if x.dtype == torch.bfloat16 else 0
+    return _lib.io_mask(x=x.dtype == torch.bfloat16)
 
 
 def conv_fwd(x, w, b, dims, act, y, w_layout=0, stats=None):
@@ -167,7 +164,7 @@ def conv_dgrad(gy, w, dims, m_channels, dx, w_layout=0, res=None):
     with timing.region(_rname("conv_dgrad", dims, f"gc{m_channels}"), conv_flops(dims, m_channels)):
         _lib.call("e2ep_conv_dgrad_acc", _lib.ptr(gy), _lib.ptr(w), d, m_channels, w_layout,
                   _lib.ptr(res), _lib.ptr(dx), _lib.ptr(ws), _lib.nbytes(ws), _lib.stream(),
-                  _IO_DX if dx.dtype == torch.bfloat16 else 0)
+                  _lib.io_mask(dx=dx.dtype == torch.bfloat16))
     return dx
 
 
@@ -317,12 +314,13 @@ def _conv_bwd_pair(gy, x, wt, dims, gc, gskip, wshape, pkeys=None):
     wsd = _ws(lib.e2ep_conv_dgrad_workspace(d, gc), gy.device)
     res = gskip.contiguous() if (gskip is not None and gc == Cin) else None
     dxg = torch.empty(N, gc, H, W, dtype=x.dtype, device=x.device)  # bf16 for a bf16-stored x
+    bf = x.dtype == torch.bfloat16
     with timing.region(_rname("conv_bwd", dims, f"gc{gc}"), conv_flops(dims, gc) + conv_flops(dims)), \
             defer.call(pkeys) as dc:
         dc.keep(wsw)  # the weight gradient's slabs, read by the deferred sum
         _lib.call("e2ep_conv_bwd", _lib.ptr(gy), _lib.ptr(x), _lib.ptr(wt), d, gc, _lib.ptr(res),
                   _lib.ptr(dxg), _lib.ptr(wsd), _lib.nbytes(wsd), splits, _lib.ptr(wsw),
-                  _lib.nbytes(wsw), _lib.ptr(dw), _lib.stream(), (_IO_X | _IO_DX) if _io_x(x) else 0)
+                  _lib.nbytes(wsw), _lib.ptr(dw), _lib.stream(), _lib.io_mask(x=bf, dx=bf))
     if gc == Cin:
         dx = dxg
     elif gskip is not None:  # channels past gc get only the skip gradient

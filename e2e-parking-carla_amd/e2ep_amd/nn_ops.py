@@ -1,6 +1,14 @@
-"""Autograd ops over the e2ep BN / resize / depthwise / pooling / SE kernels (csrc/bn.hip,
-resize.hip, dwconv.hip, pool.hip).  Each forward enqueues on torch's current HIP stream;
-each backward is the matching e2ep gradient kernel (no PyTorch arithmetic)."""
+"""Autograd ops over the e2ep kernels that are not convolutions or attention: BatchNorm +
+activation, bilinear resize, depthwise conv, pooling, squeeze-excitation and the fused MBConv
+middle (csrc/bn.hip, resize.hip, dwconv.hip, pool.hip, se.hip, mbconv_mid.hip), channel concat
+and the other small launches (small.hip), add + dropout + LayerNorm (ln.hip), nn.Linear on the
+GEMM (gemm.hip), the transformer token assembly (tokens.hip) and the channel softmax.  Each
+forward enqueues on torch's current HIP stream; each backward is the matching e2ep gradient
+kernel (no PyTorch arithmetic).
+
+The BatchNorm-fused Functions (_BnAct, _BnActDwConv, _BnSwishSE, _MBConvMid) share their
+bookkeeping: _bn_args, _bn_fwd_stats, _like, _dw_dims, _se_fwd_buffers, _se_param_grads,
+_se_workspace."""
 import ctypes
 import os
 
@@ -31,8 +39,8 @@ def _ws(nbytes, device):
 # output — the project conv's input — and the gradient at it.  Off by default: level 2 saves
 # 0.27 ms of the 18.4 ms C3 step (most of these tensors are presumably served from the 256 MB MALL, not
 # HBM) and puts the step's gradient-norm median error above the bf16 AMP comparator's
-# (0.0355 vs 0.0318; level 1: 0.0362) — profiles/r05/bf16_store_ab.txt.
-_IO_X, _IO_DY, _IO_DX = 1, 2, 4
+# (0.0355 vs 0.0318; level 1: 0.0362) — profiles/r05/bf16_store_ab.txt.  The `io` masks of the
+# calls below are _lib.io_mask's (the header's E2EP_IO_* constants).
 _BF16_STORE = [int(os.environ.get("E2EP_BF16_STORE", "0"))]
 
 
@@ -55,10 +63,40 @@ def _is_bf16(t):
     return t is not None and t.dtype == torch.bfloat16
 
 
+def _like(p, need):
+    """An uninitialised gradient buffer for p, or None when p is absent or needs none."""
+    return torch.empty_like(p) if (p is not None and need) else None
+
 
 # ------------------------------------------------------------------------------------------
 # BatchNorm2d + activation (+ residual)
 # ------------------------------------------------------------------------------------------
+def _bn_fwd_stats(x, gamma, beta, rm, rv, train, momentum, eps, part=None, tiles=0, pre=None):
+    """The (4, C) mean / invstd / scale / shift of a BatchNorm whose consumer normalises on
+    load: `pre`, the eval statistics of the forward's EvalBnBatch launch; else, training with a
+    producer's partial sums (e2ep_conv_fwd_stats / e2ep_dwconv_fwd_stats), their reduction
+    (e2ep_bn_finalize_part); else the BN's own pass over x (e2ep_bn_stats).  Only the
+    squeeze-excitation's input is ever stored bf16: _BnActDwConv's x is the expand conv's
+    output (model/efficientnet.py), which e2ep_conv_fwd writes as float, and
+    e2ep_dwconv_fwd_stats reads it as float, so there the io mask below is always 0."""
+    if pre is not None:
+        return pre
+    N, C, H, W = x.shape
+    st = torch.empty(4, C, dtype=torch.float32, device=x.device)
+    out = [_lib.ptr(st[0]), _lib.ptr(st[1]), _lib.ptr(st[2]), _lib.ptr(st[3])]
+    if part is not None and train:
+        ws = _ws(_lib.load().e2ep_bn_finalize_part_workspace(C, tiles), x.device)
+        _lib.call("e2ep_bn_finalize_part", _lib.ptr(part), tiles, _lib.ptr(gamma), _lib.ptr(beta),
+                  _lib.ptr(rm), _lib.ptr(rv), N, C, H, W, float(momentum), float(eps), *out,
+                  _lib.ptr(ws), _lib.nbytes(ws), _lib.stream())
+    else:
+        ws = _ws(_lib.load().e2ep_bn_workspace(N, C, H, W), x.device)
+        _lib.call("e2ep_bn_stats", _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(rm),
+                  _lib.ptr(rv), N, C, H, W, int(train), float(momentum), float(eps), *out,
+                  _lib.ptr(ws), _lib.nbytes(ws), _lib.stream(), _lib.io_mask(x=_is_bf16(x)))
+    return st
+
+
 class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, res, rm, rv, train, momentum, eps, act, dc_rand, dc_keep,
@@ -70,28 +108,21 @@ class _BnAct(torch.autograd.Function):
         if part is not None and train:
             # statistics from the producing conv's epilogue (e2ep_conv_fwd_stats): finalize the
             # partials, then the elementwise pass with the folded affine
-            st = torch.empty(4, C, dtype=torch.float32, device=x.device)  # mean, invstd, scale, shift
-            mean, invstd = st[0], st[1]
             with timing.region(timing.name("bn_fwd", x.shape, "_BnAct")):
-                fws = _ws(_lib.load().e2ep_bn_finalize_part_workspace(C, tiles), x.device)
-                _lib.call("e2ep_bn_finalize_part", _lib.ptr(part), tiles, _lib.ptr(gamma),
-                          _lib.ptr(beta), _lib.ptr(rm), _lib.ptr(rv), N, C, H, W, float(momentum),
-                          float(eps), _lib.ptr(st[0]), _lib.ptr(st[1]), _lib.ptr(st[2]),
-                          _lib.ptr(st[3]), _lib.ptr(fws), _lib.nbytes(fws), _lib.stream())
+                st = _bn_fwd_stats(x, gamma, beta, rm, rv, train, momentum, eps, part, tiles)
                 _lib.call("e2ep_bn_apply", _lib.ptr(x), _lib.ptr(st[2]), _lib.ptr(st[3]),
                           _lib.ptr(res), _lib.ptr(dc_rand), float(dc_keep), N, C, H, W, act,
                           _lib.ptr(y), _lib.stream())
-            ctx.save_for_backward(x, gamma, beta, res, mean, invstd, dc_rand)
-            ctx.train, ctx.act, ctx.dc_keep = train, act, dc_keep
-            return y
-        mean = torch.empty(C, dtype=torch.float32, device=x.device)
-        invstd = torch.empty_like(mean)
-        ws = _ws(_lib.load().e2ep_bn_workspace(N, C, H, W), x.device)
-        with timing.region(timing.name("bn_fwd", x.shape, "_BnAct")):
-            _lib.call("e2ep_bn_fwd", _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(res),
-                      _lib.ptr(dc_rand), float(dc_keep), _lib.ptr(rm), _lib.ptr(rv), N, C, H, W,
-                      int(train), float(momentum), float(eps), act, _lib.ptr(mean),
-                      _lib.ptr(invstd), _lib.ptr(y), _lib.ptr(ws), _lib.nbytes(ws), _lib.stream())
+            mean, invstd = st[0], st[1]
+        else:
+            mean = torch.empty(C, dtype=torch.float32, device=x.device)
+            invstd = torch.empty_like(mean)
+            ws = _ws(_lib.load().e2ep_bn_workspace(N, C, H, W), x.device)
+            with timing.region(timing.name("bn_fwd", x.shape, "_BnAct")):
+                _lib.call("e2ep_bn_fwd", _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(res),
+                          _lib.ptr(dc_rand), float(dc_keep), _lib.ptr(rm), _lib.ptr(rv), N, C, H, W,
+                          int(train), float(momentum), float(eps), act, _lib.ptr(mean),
+                          _lib.ptr(invstd), _lib.ptr(y), _lib.ptr(ws), _lib.nbytes(ws), _lib.stream())
         ctx.save_for_backward(x, gamma, beta, res, mean, invstd, dc_rand)
         ctx.train, ctx.act, ctx.dc_keep = train, act, dc_keep
         return y
@@ -102,9 +133,7 @@ class _BnAct(torch.autograd.Function):
         dy = dy.contiguous()
         N, C, H, W = x.shape
         nig = ctx.needs_input_grad
-        dx = torch.empty_like(x) if nig[0] else None
-        dg = torch.empty_like(gamma) if (gamma is not None and nig[1]) else None
-        db = torch.empty_like(beta) if (beta is not None and nig[2]) else None
+        dx, dg, db = _like(x, nig[0]), _like(gamma, nig[1]), _like(beta, nig[2])
         # no activation: the residual's gradient is dy itself (y = dc(bn(x)) + res) — hand dy
         # over instead of writing a copy
         dres_is_dy = res is not None and nig[3] and ctx.act == 0
@@ -271,14 +300,27 @@ def _eval_bn_stats(bn):
     return _EVAL_BN[-1].lookup(bn)
 
 
+def _bn_trains(bn):
+    """BatchNorm2d.forward's mode choice: batch statistics or the running ones."""
+    return bn.training or not bn.track_running_stats
+
+
 def _bn_train_and_count(bn):
-    """BatchNorm2d.forward's mode choice and num_batches_tracked increment."""
+    """_bn_trains(bn) after BatchNorm2d.forward's num_batches_tracked increment."""
     if bn.training and bn.track_running_stats:
         if _COUNTERS:
             _COUNTERS[-1].note(bn)
         else:
             bn.num_batches_tracked.add_(1)
-    return bn.training or not bn.track_running_stats
+    return _bn_trains(bn)
+
+
+def _bn_args(bn):
+    """(gamma, beta, running_mean, running_var, momentum, eps) of a BatchNorm2d module as the
+    kernels take them: no running buffers without track_running_stats, torch's default momentum."""
+    rs = bn.track_running_stats
+    return (bn.weight, bn.bias, bn.running_mean if rs else None, bn.running_var if rs else None,
+            bn.momentum if bn.momentum is not None else 0.1, bn.eps)
 
 
 def batch_norm_act(x, bn, act=None, res=None, dc_rand=None, dc_keep=1.0):
@@ -287,13 +329,11 @@ def batch_norm_act(x, bn, act=None, res=None, dc_rand=None, dc_keep=1.0):
     optional residual, then the activation."""
     _dev(x, res, dc_rand)
     train = _bn_train_and_count(bn)
-    rm = bn.running_mean if bn.track_running_stats else None
-    rv = bn.running_var if bn.track_running_stats else None
-    mom = bn.momentum if bn.momentum is not None else 0.1
+    gamma, beta, rm, rv, mom, eps = _bn_args(bn)
     if dc_rand is not None:
         dc_rand = dc_rand.contiguous()
     pp = conv.bn_partials(x) if train else None
-    return _BnAct.apply(x, bn.weight, bn.bias, res, rm, rv, train, mom, bn.eps, ACT[act],
+    return _BnAct.apply(x, gamma, beta, res, rm, rv, train, mom, eps, ACT[act],
                         dc_rand, dc_keep, *(pp or (None, 0)))
 
 
@@ -442,24 +482,10 @@ class _BnActDwConv(torch.autograd.Function):
         x = x.contiguous()
         w = w.contiguous()
         N, C, H, W, K, P, Q = dims[:7]
-        f32 = dict(dtype=torch.float32, device=x.device)
-        stats = pre if pre is not None else torch.empty(4, C, **f32)  # mean, invstd, scale, shift
         s = _lib.stream()
         with timing.region(timing.name("bn_fwd", x.shape, "_BnActDwConv")):
-            if pre is not None:  # eval statistics of the forward's EvalBnBatch launch
-                pass
-            elif part is not None and train:  # partials from the expand conv's epilogue
-                fws = _ws(_lib.load().e2ep_bn_finalize_part_workspace(C, tiles), x.device)
-                _lib.call("e2ep_bn_finalize_part", _lib.ptr(part), tiles, _lib.ptr(gamma),
-                          _lib.ptr(beta), _lib.ptr(rm), _lib.ptr(rv), N, C, H, W, float(momentum),
-                          float(eps), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(stats[2]),
-                          _lib.ptr(stats[3]), _lib.ptr(fws), _lib.nbytes(fws), s)
-            else:
-                ws = _ws(_lib.load().e2ep_bn_workspace(N, C, H, W), x.device)
-                _lib.call("e2ep_bn_stats", _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(rm),
-                          _lib.ptr(rv), N, C, H, W, int(train), float(momentum), float(eps),
-                          _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(stats[2]),
-                          _lib.ptr(stats[3]), _lib.ptr(ws), _lib.nbytes(ws), s, 0)
+            # partials, when given, are from the expand conv's epilogue
+            stats = _bn_fwd_stats(x, gamma, beta, rm, rv, train, momentum, eps, part, tiles, pre)
         # bf16 storage of the depthwise output (C3 training, _store_bf16)
         d = _lib.dims(dims)
         # every kernel on either side of this layer must take the bf16 masks, or the layer
@@ -469,7 +495,7 @@ class _BnActDwConv(torch.autograd.Function):
         with timing.region(timing.name("dwconv_fwd", x.shape, "_BnActDwConv")):
             _lib.call("e2ep_dwconv_fwd_stats", _lib.ptr(x), _lib.ptr(w), d, _lib.ptr(stats[2]),
                       _lib.ptr(stats[3]), act, _lib.ptr(y), _lib.ptr(ystats), _lib.nbytes(ystats), s,
-                      _IO_DX if hb else 0)
+                      _lib.io_mask(dx=hb))
         ctx.save_for_backward(x, gamma, beta, w, stats)
         ctx.dims, ctx.train, ctx.act = dims, train, act
         return y
@@ -498,7 +524,7 @@ class _BnActDwConv(torch.autograd.Function):
                 _lib.call("e2ep_dwconv_bwd", _lib.ptr(gy), _lib.ptr(x), _lib.ptr(w), d,
                           _lib.ptr(stats[2]), _lib.ptr(stats[3]), ctx.act, _lib.ptr(dt),
                           _lib.ptr(wsw), _lib.nbytes(wsw), _lib.ptr(dw), s,
-                          (_IO_DY | _IO_DX) if hb else 0)
+                          _lib.io_mask(dy=hb, dx=hb))
         elif nig[9]:  # weight gradient on the side stream (conv._Fork)
             dw = torch.empty_like(w)
             wsw = _ws(_lib.load().e2ep_dwconv_wgrad_workspace(d), x.device)
@@ -507,37 +533,40 @@ class _BnActDwConv(torch.autograd.Function):
             with fork, timing.region(timing.name("dwconv_wgrad", gy.shape, "_BnActDwConv")):
                 _lib.call("e2ep_dwconv_wgrad", _lib.ptr(gy), _lib.ptr(x), d, _lib.ptr(stats[2]),
                           _lib.ptr(stats[3]), ctx.act, _lib.ptr(wsw), _lib.nbytes(wsw), _lib.ptr(dw), _lib.stream(),
-                          _IO_DY if hb else 0)
+                          _lib.io_mask(dy=hb))
         if want_t:
             if not paired:
                 dt = torch.empty(x.shape, dtype=tdt, device=x.device)  # gradient at the activation output
                 with timing.region(timing.name("dwconv_dgrad", gy.shape, "_BnActDwConv")):
                     _lib.call("e2ep_dwconv_dgrad", _lib.ptr(gy), _lib.ptr(w), d, _lib.ptr(dt), s,
-                              (_IO_DY | _IO_DX) if hb else 0)
-            dx = torch.empty_like(x) if nig[0] else None
-            dg = torch.empty_like(gamma) if (gamma is not None and nig[1]) else None
-            db = torch.empty_like(beta) if (beta is not None and nig[2]) else None
+                              _lib.io_mask(dy=hb, dx=hb))
+            dx, dg, db = _like(x, nig[0]), _like(gamma, nig[1]), _like(beta, nig[2])
             ws = _ws(_lib.load().e2ep_bn_workspace(N, C, H, W), x.device)
             with timing.region(timing.name("bn_bwd", x.shape, "_BnActDwConv")):
                 _lib.call("e2ep_bn_bwd", _lib.ptr(x), _lib.ptr(dt), _lib.ptr(stats[0]),
                           _lib.ptr(stats[1]), _lib.ptr(gamma), _lib.ptr(beta), None, None, 1.0,
                           None, None, N, C, H, W, int(ctx.train), ctx.act, _lib.ptr(dx), _lib.ptr(dg),
-                          _lib.ptr(db), None, _lib.ptr(ws), _lib.nbytes(ws), s, _IO_DY if hb else 0)
+                          _lib.ptr(db), None, _lib.ptr(ws), _lib.nbytes(ws), s, _lib.io_mask(dy=hb))
         if fork is not None:
             fork.join()
         return dx, dg, db, None, None, None, None, None, None, dw, None, None, None, None, None
+
+
+def _dw_dims(N, C, H, W, w, stride, pad):
+    """dims[10] of the depthwise entry points for an input [N, C, H, W], w [C, 1, K, K] and
+    pad = (left, right, top, bottom)."""
+    K = w.shape[-1]
+    l, r, t, b = pad
+    P = (H + t + b - K) // stride + 1
+    Q = (W + l + r - K) // stride + 1
+    return (N, C, H, W, K, P, Q, stride, t, l)
 
 
 def depthwise_conv2d(x, w, stride, pad, bn_stats=False):
     """pad = (left, right, top, bottom); w [C, 1, K, K].  bn_stats: see
     bn_act_depthwise_conv2d."""
     _dev(x)
-    N, C, H, W = x.shape
-    K = w.shape[-1]
-    l, r, t, b = pad
-    P = (H + t + b - K) // stride + 1
-    Q = (W + l + r - K) // stride + 1
-    dims = (N, C, H, W, K, P, Q, stride, t, l)
+    dims = _dw_dims(*x.shape, w, stride, pad)
     ys, tiles = _dw_stats_buffer(dims, x.device, bn_stats)
     y = _DwConv.apply(x, w, dims, ys)
     if ys is not None:
@@ -563,18 +592,11 @@ def bn_act_depthwise_conv2d(x, bn, act, w, stride, pad, bn_stats=False):
     depthwise kernel, attached as for conv.conv2d(bn_stats=True))."""
     _dev(x)
     train = _bn_train_and_count(bn)
-    rm = bn.running_mean if bn.track_running_stats else None
-    rv = bn.running_var if bn.track_running_stats else None
-    mom = bn.momentum if bn.momentum is not None else 0.1
-    N, C, H, W = x.shape
-    K = w.shape[-1]
-    l, r, t, b = pad
-    P = (H + t + b - K) // stride + 1
-    Q = (W + l + r - K) // stride + 1
+    gamma, beta, rm, rv, mom, eps = _bn_args(bn)
     pp = conv.bn_partials(x) if train else None
-    dims = (N, C, H, W, K, P, Q, stride, t, l)
+    dims = _dw_dims(*x.shape, w, stride, pad)
     ys, tiles = _dw_stats_buffer(dims, x.device, bn_stats)
-    y = _BnActDwConv.apply(x, bn.weight, bn.bias, rm, rv, train, mom, bn.eps, ACT[act], w, dims,
+    y = _BnActDwConv.apply(x, gamma, beta, rm, rv, train, mom, eps, ACT[act], w, dims,
                            *(pp or (None, 0)), ys, None if train else _eval_bn_stats(bn))
     if ys is not None:
         y._e2ep_bn_part = (ys, tiles)
@@ -671,18 +693,43 @@ def se_gate(x, a):
 # ------------------------------------------------------------------------------------------
 # squeeze-and-excitation (fused)
 # ------------------------------------------------------------------------------------------
+def _se_fwd_buffers(N, C, w1, w2, device):
+    """(pooled [N,C], hpre [N,sq], a [N,C]), the forward outputs the backward reads, and the
+    two 1x1 conv weights as the [sq,C] / [C,sq] matrices the kernels take."""
+    sq = w1.shape[0]
+    f32 = dict(dtype=torch.float32, device=device)
+    return (torch.empty(N, C, **f32), torch.empty(N, sq, **f32), torch.empty(N, C, **f32),
+            w1.reshape(sq, C).contiguous(), w2.reshape(C, sq).contiguous())
+
+
+def _se_param_grads(shapes, need, device):
+    """(dw1, db1, dw2, db2) buffers of a squeeze-excitation backward, None where not needed:
+    shapes = ctx.shapes (w1's and w2's shapes, whether b1 / b2 exist), need = the Function's
+    needs_input_grad entries of (w1, b1, w2, b2)."""
+    w1s, w2s, hb1, hb2 = shapes
+    f32 = dict(dtype=torch.float32, device=device)
+    return (torch.empty(w1s, **f32) if need[0] else None,
+            torch.empty(w1s[0], **f32) if (hb1 and need[1]) else None,
+            torch.empty(w2s, **f32) if need[2] else None,
+            torch.empty(w2s[0], **f32) if (hb2 and need[3]) else None)
+
+
+def _se_workspace(N, C, sq, device):
+    """e2ep_se_bwd's float workspace (include/e2ep.h, the squeeze-excitation contract:
+    2*N*C + 17*N*sq floats): da and the pooled gradient [N,C] each, then dhpre [N,sq] and up
+    to 16 partial dh [N,sq] over 256-channel spans (C <= 4096; csrc/se.hip).  The deferred
+    weight gradients read da and dhpre from it, so callers keep it (defer.call ... keep)."""
+    return torch.empty(2 * N * C + 17 * N * sq, dtype=torch.float32, device=device)
+
+
 class _SqueezeExcite(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
         x = x.contiguous()
         N, C, H, W = x.shape
         sq = w1.shape[0]
-        dev = x.device
-        pooled = torch.empty(N, C, dtype=torch.float32, device=dev)
-        hpre = torch.empty(N, sq, dtype=torch.float32, device=dev)
-        a = torch.empty(N, C, dtype=torch.float32, device=dev)
+        pooled, hpre, a, w1c, w2c = _se_fwd_buffers(N, C, w1, w2, x.device)
         y = torch.empty_like(x)
-        w1c, w2c = w1.reshape(sq, C).contiguous(), w2.reshape(C, sq).contiguous()
         with timing.region(timing.name("se_fwd", x.shape, "_SqueezeExcite")):
             _lib.call("e2ep_se_fwd", _lib.ptr(x), None, None, _lib.ptr(w1c), _lib.ptr(b1), _lib.ptr(w2c),
                       _lib.ptr(b2), N, C, H * W, sq, _lib.ptr(pooled), _lib.ptr(hpre), _lib.ptr(a),
@@ -695,17 +742,12 @@ class _SqueezeExcite(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w1c, w2c, pooled, hpre, a = ctx.saved_tensors
-        w1s, w2s, hb1, hb2 = ctx.shapes
         N, C, H, W = x.shape
         sq = w1c.shape[0]
         nig = ctx.needs_input_grad
-        dev = x.device
-        dx = torch.empty_like(x) if nig[0] else None
-        dw1 = torch.empty(w1s, dtype=torch.float32, device=dev) if nig[1] else None
-        db1 = torch.empty(sq, dtype=torch.float32, device=dev) if (hb1 and nig[2]) else None
-        dw2 = torch.empty(w2s, dtype=torch.float32, device=dev) if nig[3] else None
-        db2 = torch.empty(C, dtype=torch.float32, device=dev) if (hb2 and nig[4]) else None
-        ws = torch.empty(2 * N * C + 17 * N * sq, dtype=torch.float32, device=dev)
+        dx = _like(x, nig[0])
+        dw1, db1, dw2, db2 = _se_param_grads(ctx.shapes, nig[1:5], x.device)
+        ws = _se_workspace(N, C, sq, x.device)
         with timing.region(timing.name("se_bwd", x.shape, "_SqueezeExcite")), \
                 defer.call(ctx.pkeys) as dc:
             dc.keep(pooled, hpre, ws)  # read by the deferred weight gradients (da, dhpre in ws)
@@ -741,37 +783,21 @@ class _BnSwishSE(torch.autograd.Function):
         N, C, H, W = x.shape
         sq = w1.shape[0]
         dev = x.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        stats = pre if pre is not None else torch.empty(4, C, **f32)  # mean, invstd, scale, shift
         s = _lib.stream()
         with timing.region(timing.name("bn_fwd", x.shape, "_BnSwishSE")):
-            if pre is not None:  # eval statistics of the forward's EvalBnBatch launch
-                pass
-            elif part is not None and train:  # partials from the depthwise kernel
-                fws = _ws(_lib.load().e2ep_bn_finalize_part_workspace(C, tiles), x.device)
-                _lib.call("e2ep_bn_finalize_part", _lib.ptr(part), tiles, _lib.ptr(gamma),
-                          _lib.ptr(beta), _lib.ptr(rm), _lib.ptr(rv), N, C, H, W, float(momentum),
-                          float(eps), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(stats[2]),
-                          _lib.ptr(stats[3]), _lib.ptr(fws), _lib.nbytes(fws), s)
-            else:
-                ws = _ws(_lib.load().e2ep_bn_workspace(N, C, H, W), dev)
-                _lib.call("e2ep_bn_stats", _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(rm),
-                          _lib.ptr(rv), N, C, H, W, int(train), float(momentum), float(eps),
-                          _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(stats[2]),
-                          _lib.ptr(stats[3]), _lib.ptr(ws), _lib.nbytes(ws), s,
-                          _IO_X if _is_bf16(x) else 0)
-        pooled, hpre, a = torch.empty(N, C, **f32), torch.empty(N, sq, **f32), torch.empty(N, C, **f32)
+            # partials, when given, are from the depthwise kernel
+            stats = _bn_fwd_stats(x, gamma, beta, rm, rv, train, momentum, eps, part, tiles, pre)
+        pooled, hpre, a, w1c, w2c = _se_fwd_buffers(N, C, w1, w2, dev)
         # a bf16-stored input (bf16 storage, _store_bf16): at level 2 the output — the project
         # conv's input — is stored bf16 too
         hb = _is_bf16(x)
         yb = hb and _BF16_STORE[0] >= 2  # the output stored bf16 as well (level 2)
         y = torch.empty(x.shape, dtype=torch.bfloat16 if yb else torch.float32, device=dev)
-        w1c, w2c = w1.reshape(sq, C).contiguous(), w2.reshape(C, sq).contiguous()
         with timing.region(timing.name("se_fwd", x.shape, "_BnSwishSE")):
             _lib.call("e2ep_se_fwd", _lib.ptr(x), _lib.ptr(stats[2]), _lib.ptr(stats[3]),
                       _lib.ptr(w1c), _lib.ptr(b1), _lib.ptr(w2c), _lib.ptr(b2), N, C, H * W, sq,
                       _lib.ptr(pooled), _lib.ptr(hpre), _lib.ptr(a), _lib.ptr(y), s,
-                      (_IO_X | (_IO_DX if yb else 0)) if hb else 0)
+                      _lib.io_mask(x=hb, dx=yb))
         ctx.save_for_backward(x, gamma, beta, stats, w1c, w2c, pooled, hpre, a)
         ctx.shapes = (w1.shape, w2.shape, b1 is not None, b2 is not None)
         ctx.pkeys = defer.note(w1, b1, w2, b2)
@@ -781,26 +807,20 @@ class _BnSwishSE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, gamma, beta, stats, w1c, w2c, pooled, hpre, a = ctx.saved_tensors
-        w1s, w2s, hb1, hb2 = ctx.shapes
         N, C, H, W = x.shape
         sq = w1c.shape[0]
         nig = ctx.needs_input_grad
         dev = x.device
-        f32 = dict(dtype=torch.float32, device=dev)
         dy = dy.contiguous()
         s = _lib.stream()
-        dw1 = torch.empty(w1s, **f32) if nig[8] else None
-        db1 = torch.empty(sq, **f32) if (hb1 and nig[9]) else None
-        dw2 = torch.empty(w2s, **f32) if nig[10] else None
-        db2 = torch.empty(C, **f32) if (hb2 and nig[11]) else None
-        dpooled = torch.empty(N, C, **f32)
-        ws = torch.empty(2 * N * C + 17 * N * sq, **f32)
-        dx = torch.empty_like(x) if nig[0] else None  # bf16 with a bf16-stored x
-        dg = torch.empty_like(gamma) if (gamma is not None and nig[1]) else None
-        db = torch.empty_like(beta) if (beta is not None and nig[2]) else None
+        dw1, db1, dw2, db2 = _se_param_grads(ctx.shapes, nig[8:12], dev)
+        dpooled = torch.empty(N, C, dtype=torch.float32, device=dev)
+        ws = _se_workspace(N, C, sq, dev)
+        dx = _like(x, nig[0])  # bf16 with a bf16-stored x
+        dg, db = _like(gamma, nig[1]), _like(beta, nig[2])
         hb = _is_bf16(x)
         # storage of the incoming gradient (bf16 at a bf16-stored output)
-        io_in = (_IO_X | (_IO_DY if _is_bf16(dy) else 0)) if hb else 0
+        io_in = _lib.io_mask(x=hb, dy=hb and _is_bf16(dy))
         # training BN on the split path: its channel sums are taken in the SE's da pass
         # (e2ep_se_bwd_bn), so the BN backward is its apply pass alone
         fused = (_SE_BN_SUMS[0] and ctx.train and dx is not None
@@ -820,7 +840,7 @@ class _BnSwishSE(torch.autograd.Function):
                 _lib.call("e2ep_bn_bwd_planes", _lib.ptr(x), _lib.ptr(dy), _lib.ptr(stats[0]),
                           _lib.ptr(stats[1]), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(a),
                           _lib.ptr(dpooled), _lib.ptr(planes), N, C, H, W, ACT["swish"],
-                          _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), s, (io_in | _IO_DX) if hb else 0)
+                          _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), s, io_in | _lib.io_mask(dx=hb))
             return dx, dg, db, None, None, None, None, None, dw1, db1, dw2, db2, None, None, None
         with timing.region(timing.name("se_bwd", x.shape, "_BnSwishSE")), \
                 defer.call(ctx.pkeys) as dc:
@@ -837,7 +857,7 @@ class _BnSwishSE(torch.autograd.Function):
                           _lib.ptr(stats[1]), _lib.ptr(gamma), _lib.ptr(beta), None, None, 1.0,
                           _lib.ptr(a), _lib.ptr(dpooled), N, C, H, W, int(ctx.train), ACT["swish"],
                           _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), None, _lib.ptr(bws), _lib.nbytes(bws), s,
-                          (io_in | _IO_DX) if hb else 0)
+                          io_in | _lib.io_mask(dx=hb))
         return dx, dg, db, None, None, None, None, None, dw1, db1, dw2, db2, None, None, None
 
 
@@ -845,11 +865,9 @@ def bn_swish_squeeze_excite(x, bn, w1, b1, w2, b2):
     """squeeze_excite(batch_norm_act(x, bn, 'swish'), w1, b1, w2, b2) as one fused op."""
     _dev(x)
     train = _bn_train_and_count(bn)
-    rm = bn.running_mean if bn.track_running_stats else None
-    rv = bn.running_var if bn.track_running_stats else None
-    mom = bn.momentum if bn.momentum is not None else 0.1
+    gamma, beta, rm, rv, mom, eps = _bn_args(bn)
     pp = conv.bn_partials(x) if train else None
-    return _BnSwishSE.apply(x, bn.weight, bn.bias, rm, rv, train, mom, bn.eps, w1, b1, w2, b2,
+    return _BnSwishSE.apply(x, gamma, beta, rm, rv, train, mom, eps, w1, b1, w2, b2,
                             *(pp or (None, 0)), None if train else _eval_bn_stats(bn))
 
 
@@ -857,25 +875,13 @@ def bn_swish_squeeze_excite(x, bn, w1, b1, w2, b2):
 # MBConv middle on 16x16 maps: _bn0 -> swish -> depthwise -> _bn1 -> swish -> SE, the chain up
 # to the SE squeeze in one launch per direction (csrc/mbconv_mid.hip, e2ep_tune key 36)
 # ------------------------------------------------------------------------------------------
-def _bn_trains(bn):
-    return bn.training or not bn.track_running_stats
-
-
-def _mid_dims(N, C, H, W, w, stride, pad):
-    K = w.shape[-1]
-    l, r, t, b = pad
-    P = (H + t + b - K) // stride + 1
-    Q = (W + l + r - K) // stride + 1
-    return (N, C, H, W, K, P, Q, stride, t, l)
-
-
 def mbconv_mid_ok(shape, dtype, bn0, bn1, w, stride, pad):
     """True when bn_act_depthwise_conv2d + bn_swish_squeeze_excite on an input of `shape` run
     as the fused op (mbconv_mid): training statistics for both BatchNorms, fp32 storage, and a
     shape e2ep_mbconv_mid_ok takes."""
     if dtype != torch.float32 or not (_bn_trains(bn0) and _bn_trains(bn1)) or _store_bf16(True):
         return False
-    return _lib.load().e2ep_mbconv_mid_ok(_lib.dims(_mid_dims(*shape, w, stride, pad))) == 1
+    return _lib.load().e2ep_mbconv_mid_ok(_lib.dims(_dw_dims(*shape, w, stride, pad))) == 1
 
 
 class _MBConvMid(torch.autograd.Function):
@@ -894,15 +900,15 @@ class _MBConvMid(torch.autograd.Function):
         sq = w1.shape[0]
         f32 = dict(dtype=torch.float32, device=x.device)
         st0, st1 = torch.empty(4, C, **f32), torch.empty(4, C, **f32)  # mean, invstd, scale, shift
-        y1, pooled = torch.empty_like(x), torch.empty(N, C, **f32)
+        y1 = torch.empty_like(x)
+        pooled, hpre, a, w1c, w2c = _se_fwd_buffers(N, C, w1, w2, x.device)
         s = _lib.stream()
         with timing.region(timing.name("mbconv_mid_fwd", x.shape, "_MBConvMid")):
             _lib.call("e2ep_mbconv_mid_fwd", _lib.ptr(x), _lib.ptr(w), _lib.dims(dims), _lib.ptr(g0),
                       _lib.ptr(b0), _lib.ptr(rm0), _lib.ptr(rv0), float(mom0), float(eps0),
                       _lib.ptr(st0), _lib.ptr(g1), _lib.ptr(b1), _lib.ptr(rm1), _lib.ptr(rv1),
                       float(mom1), float(eps1), _lib.ptr(st1), _lib.ptr(y1), _lib.ptr(pooled), s)
-        hpre, a, y = torch.empty(N, sq, **f32), torch.empty(N, C, **f32), torch.empty_like(x)
-        w1c, w2c = w1.reshape(sq, C).contiguous(), w2.reshape(C, sq).contiguous()
+        y = torch.empty_like(x)
         with timing.region(timing.name("se_fwd", x.shape, "_MBConvMid")):
             _lib.call("e2ep_se_fwd_pooled", _lib.ptr(y1), _lib.ptr(st1[2]), _lib.ptr(st1[3]),
                       _lib.ptr(w1c), _lib.ptr(sb1), _lib.ptr(w2c), _lib.ptr(sb2), N, C, 256, sq,
@@ -916,19 +922,14 @@ class _MBConvMid(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, y1, w, g0, b0, st0, g1, b1, st1, w1c, w2c, pooled, hpre, a = ctx.saved_tensors
-        w1s, w2s, hb1, hb2 = ctx.shapes
         N, C = ctx.dims[:2]
         sq = w1c.shape[0]
         nig = ctx.needs_input_grad
-        f32 = dict(dtype=torch.float32, device=x.device)
         dy = dy.contiguous()
         s = _lib.stream()
-        dw1 = torch.empty(w1s, **f32) if nig[15] else None
-        dsb1 = torch.empty(sq, **f32) if (hb1 and nig[16]) else None
-        dw2 = torch.empty(w2s, **f32) if nig[17] else None
-        dsb2 = torch.empty(C, **f32) if (hb2 and nig[18]) else None
-        dpooled = torch.empty(N, C, **f32)
-        ws = torch.empty(2 * N * C + 17 * N * sq, **f32)
+        dw1, dsb1, dw2, dsb2 = _se_param_grads(ctx.shapes, nig[15:19], x.device)
+        dpooled = torch.empty(N, C, dtype=torch.float32, device=x.device)
+        ws = _se_workspace(N, C, sq, x.device)
         with timing.region(timing.name("se_bwd", x.shape, "_MBConvMid")), \
                 defer.call(ctx.pkeys) as dc:
             dc.keep(pooled, hpre, ws)  # read by the deferred weight gradients
@@ -937,10 +938,8 @@ class _MBConvMid(torch.autograd.Function):
                       N, C, 256, sq, None, _lib.ptr(dpooled), _lib.ptr(dw1), _lib.ptr(dsb1),
                       _lib.ptr(dw2), _lib.ptr(dsb2), _lib.ptr(ws), s, 0)
         dx, dw = torch.empty_like(x), torch.empty_like(w)
-        dg0 = torch.empty_like(g0) if (g0 is not None and nig[1]) else None
-        db0 = torch.empty_like(b0) if (b0 is not None and nig[2]) else None
-        dg1 = torch.empty_like(g1) if (g1 is not None and nig[9]) else None
-        db1 = torch.empty_like(b1) if (b1 is not None and nig[10]) else None
+        dg0, db0 = _like(g0, nig[1]), _like(b0, nig[2])
+        dg1, db1 = _like(g1, nig[9]), _like(b1, nig[10])
         with timing.region(timing.name("mbconv_mid_bwd", x.shape, "_MBConvMid")):
             _lib.call("e2ep_mbconv_mid_bwd", _lib.ptr(dy), _lib.ptr(a), _lib.ptr(dpooled),
                       _lib.ptr(y1), _lib.ptr(x), _lib.ptr(w), _lib.dims(ctx.dims), _lib.ptr(st1),
@@ -957,14 +956,8 @@ def mbconv_mid(x, bn0, w, stride, pad, bn1, w1, b1, w2, b2):
     _dev(x)
     _bn_train_and_count(bn0)
     _bn_train_and_count(bn1)
-
-    def args(bn):
-        rs = bn.track_running_stats
-        return (bn.weight, bn.bias, bn.running_mean if rs else None, bn.running_var if rs else None,
-                bn.momentum if bn.momentum is not None else 0.1, bn.eps)
-
-    dims = _mid_dims(*x.shape, w, stride, pad)
-    return _MBConvMid.apply(x, *args(bn0), w, dims, *args(bn1), w1, b1, w2, b2)
+    dims = _dw_dims(*x.shape, w, stride, pad)
+    return _MBConvMid.apply(x, *_bn_args(bn0), w, dims, *_bn_args(bn1), w1, b1, w2, b2)
 
 
 def squeeze_excite(x, w1, b1, w2, b2):
@@ -1121,10 +1114,8 @@ class _AddDropLN(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, rstd, gamma, mask = ctx.saved_tensors
         nig = ctx.needs_input_grad
-        da = torch.empty_like(x) if nig[0] else None
-        db = torch.empty_like(x) if nig[1] else None
-        dg = torch.empty_like(gamma) if (gamma is not None and nig[2]) else None
-        dbeta = torch.empty_like(gamma) if (gamma is not None and nig[3]) else None
+        da, db = _like(x, nig[0]), _like(x, nig[1])
+        dg, dbeta = _like(gamma, nig[2]), _like(gamma, nig[3])
         ws = _ws(_lib.load().e2ep_add_drop_ln_bwd_workspace(ctx.rows, ctx.E), x.device)
         with timing.region(timing.name("ln_bwd", x.shape, "_AddDropLN")), \
                 defer.call(ctx.pkeys) as dc:
@@ -1178,6 +1169,22 @@ def gemm(A, a_kcontig, B, b_kcontig, M, N, K, bias=None, cadd=None, out=None, re
     return out
 
 
+def _rows2(x):
+    """x as a dense (rows, K) matrix over its last dim (a view where x allows one)."""
+    K = x.shape[-1]
+    x2 = x.reshape(-1, K)
+    return x2 if (x2.stride(1) == 1 and x2.stride(0) == K) else x2.contiguous()
+
+
+def _skip_rows(gskip, M, K):
+    """The residual's gradient as the (M, K) addend of the input-gradient GEMM's epilogue (unit
+    inner stride), or None."""
+    if gskip is None:
+        return None
+    cadd = gskip.reshape(M, K)
+    return cadd if cadd.stride(1) == 1 else cadd.contiguous()
+
+
 class _Linear(torch.autograd.Function):
     """y = x W^T + b (+ ReLU).  All three GEMMs are e2ep_gemm: forward (bias and ReLU in the
     epilogue), dX = dY W (the residual's gradient added in the epilogue when skip is used),
@@ -1186,10 +1193,8 @@ class _Linear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, skip=False, relu=False):
-        K = x.shape[-1]
-        x2 = x.reshape(-1, K)
-        if x2.stride(1) != 1 or x2.stride(0) != K:
-            x2 = x2.contiguous()
+        x2 = _rows2(x)
+        K = x2.shape[1]
         N = weight.shape[0]
         y = gemm(x2, True, weight, True, x2.shape[0], N, K, bias=bias, relu=relu, tag="linear_fwd")
         ctx.save_for_backward(x2, weight, y if relu else None)
@@ -1203,11 +1208,7 @@ class _Linear(torch.autograd.Function):
     def backward(ctx, gy, gskip=None):
         x2, weight, y = ctx.saved_tensors
         nig = ctx.needs_input_grad
-        M, K = x2.shape
-        N = weight.shape[0]
-        g2 = gy.reshape(M, N)
-        if g2.stride(1) != 1 or g2.stride(0) != N:
-            g2 = g2.contiguous()
+        g2 = _rows2(gy)
         if ctx.relu:  # dY * [y > 0] (relu derivative on the output), one e2ep launch
             gr = torch.empty_like(g2)
             _lib.call("e2ep_act_bwd", _lib.ptr(y), _lib.ptr(g2), g2.numel(), 1, _lib.ptr(gr),
@@ -1234,9 +1235,7 @@ def _linear_bwd(g2, x2, weight, want_x, want_w, want_b, gskip=None, dw=None, db=
             dw = torch.empty(N, K, dtype=torch.float32, device=g2.device)
         if db is None:
             db = torch.empty(N, dtype=torch.float32, device=g2.device)
-        cadd = gskip.reshape(M, K) if gskip is not None else None
-        if cadd is not None and cadd.stride(1) != 1:
-            cadd = cadd.contiguous()
+        cadd = _skip_rows(gskip, M, K)
         dx = torch.empty(M, K, dtype=torch.float32, device=g2.device)
         lib = _lib.load()
         wsx = _ws(lib.e2ep_gemm_workspace(M, K, N), g2.device)
@@ -1275,19 +1274,10 @@ def _linear_bwd(g2, x2, weight, want_x, want_w, want_b, gskip=None, dw=None, db=
                 _lib.call("e2ep_col_sum", _lib.ptr(g2), M, N, _lib.ptr(db), _lib.ptr(wsb),
                           _lib.stream())
     if want_x:
-        cadd = gskip.reshape(M, K) if gskip is not None else None
-        if cadd is not None and cadd.stride(1) != 1:
-            cadd = cadd.contiguous()
-        dx = gemm(g2, True, weight, False, M, K, N, cadd=cadd, tag="linear_dgrad")
+        dx = gemm(g2, True, weight, False, M, K, N, cadd=_skip_rows(gskip, M, K), tag="linear_dgrad")
     if fork is not None:
         fork.join()
     return dx, (dw if want_w else None), (db if want_b else None)
-
-
-def _rows2(x):
-    K = x.shape[-1]
-    x2 = x.reshape(-1, K)
-    return x2 if (x2.stride(1) == 1 and x2.stride(0) == K) else x2.contiguous()
 
 
 class _InProjQKV(torch.autograd.Function):

@@ -2,13 +2,12 @@
 e2ep_amd.attention.MultiheadAttention without any change to its state dict, initial weights
 or RNG stream; e2ep_attn_weights is declared and bound; on CPU tensors the new class is torch's
 module."""
+import ctypes
 import os
-import re
 
 import torch
 from torch import nn
 
-from conftest import ROOT
 from helpers import meta
 
 
@@ -74,12 +73,12 @@ def test_new_class_adds_no_state():
 
 def test_entry_point_declared_and_bound():
     from e2ep_amd import _lib
-    src = open(os.path.join(ROOT, "include", "e2ep.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    assert re.search(r"\bint\s+e2ep_attn_weights\s*\(", src)
-    assert "e2ep_attn_weights" in _lib.SIGNATURES
+    assert "e2ep_attn_weights" in _lib.SIGNATURES  # read from include/e2ep.h
     res, args = _lib.SIGNATURES["e2ep_attn_weights"]
+    assert res is ctypes.c_int
     assert len(args) == 18  # q, k, lse, 9 ints, scale, causal, key_pad, average, w, stream
+    if os.path.exists(_lib.LIB_PATH):
+        assert hasattr(_lib.load(), "e2ep_attn_weights")
 
 
 def test_cpu_tensors_take_the_stock_forward():

@@ -1,7 +1,6 @@
 """Host side of gradient clipping / step skipping / accumulation: entry points, config keys,
 the Lightning clipping hook and TrainStep's argument check.  No GPU call is made."""
 import os
-import re
 import types
 
 import pytest
@@ -18,14 +17,9 @@ def test_library_exports_the_new_entry_points():
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail("libe2ep_hip.so not built; run __graft_entry__.build()")
     lib = _lib.load()
-    src = open(os.path.join(ROOT, "include", "e2ep.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    for name in NEW:
+    for name in NEW:  # the binding is read from include/e2ep.h (argument types: test_abi_cpu.py)
+        assert name in _lib.SIGNATURES, f"{name} not declared in include/e2ep.h"
         assert hasattr(lib, name), name
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, src)
-        assert m, f"{name} not declared in include/e2ep.h"
-        res, args = _lib.SIGNATURES[name]
-        assert len(args) == len(m.group(1).split(",")), name
     assert lib.e2ep_abi_version() == 4  # additive: the existing entry points are unchanged
     assert len(_lib.SIGNATURES["e2ep_adam_step"][1]) == 17
     assert len(_lib.SIGNATURES["e2ep_grad_gather"][1]) == 6
