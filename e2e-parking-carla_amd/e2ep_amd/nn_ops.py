@@ -63,6 +63,14 @@ def _is_bf16(t):
     return t is not None and t.dtype == torch.bfloat16
 
 
+def _dense16(t):
+    """t dense at a 16-byte-aligned address, as the float4 entry points require.  .contiguous()
+    alone leaves a dense view where it is (flat[1:1 + n].view(shape) sits 4 bytes off); such an
+    operand is copied into a fresh allocation."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _like(p, need):
     """An uninitialised gradient buffer for p, or None when p is absent or needs none."""
     return torch.empty_like(p) if (p is not None and need) else None
@@ -973,7 +981,7 @@ def squeeze_excite(x, w1, b1, w2, b2):
 class _CatChannels(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *xs):
-        xs = [x.contiguous() for x in xs]
+        xs = [_dense16(x) for x in xs]
         N, _, H, W = xs[0].shape
         chans = [x.shape[1] for x in xs]
         y = torch.empty(N, sum(chans), H, W, dtype=torch.float32, device=xs[0].device)
@@ -985,7 +993,7 @@ class _CatChannels(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        g = g.contiguous()
+        g = _dense16(g)
         N, _, H, W = g.shape
         outs = [torch.empty(N, c, H, W, dtype=torch.float32, device=g.device) for c in ctx.chans]
         n = len(outs)
@@ -997,7 +1005,8 @@ class _CatChannels(torch.autograd.Function):
 def cat_channels(xs):
     """torch.cat(xs, 1) of NCHW fp32 device tensors as one e2ep launch, and its backward as
     one launch writing every piece's gradient contiguous (no slice copies downstream).  Falls
-    back to torch.cat outside the kernel's range (more than 8 pieces, H*W % 4 != 0)."""
+    back to torch.cat outside the kernel's range (more than 8 pieces, H*W % 4 != 0); a piece or
+    gradient off 16-byte alignment is copied first (_dense16)."""
     _dev(*xs)
     if (len(xs) > 8 or any(x.dim() != 4 or x.dtype != torch.float32 for x in xs)
             or (xs[0].shape[2] * xs[0].shape[3]) % 4):
@@ -1353,7 +1362,7 @@ class _ReluDropout(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, seed = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = _dense16(dy)
         dx = torch.empty_like(x)
         _lib.call("e2ep_relu_dropout_bwd", _lib.ptr(x), _lib.ptr(dy), x.numel(), ctx.p,
                   _lib.ptr(seed), _lib.ptr(dx), _lib.stream())
@@ -1365,7 +1374,7 @@ def relu_dropout(x, p=0.0, seed=None):
     The mask is a hash of a per-call device seed (drawn here when p > 0 and none is given:
     graph-capturable) and the element index."""
     _dev(x)
-    x = x.contiguous()
+    x = _dense16(x)
     if p > 0.0 and seed is None:
         seed = rng.seed(x.device)
     return _ReluDropout.apply(x, float(p), seed)

@@ -353,7 +353,9 @@ int e2ep_act_bwd(const float *x, const float *dy, long long n, int act, float *d
  * [N][sum chans][HW] (ASPP branches, reference model/convolutions.py:262-263; UpsamplingConcat,
  * model/convolutions.py:281-282), and its backward: the split of dst-shaped `src` into n
  * contiguous pieces (torch's CatBackward slices + .contiguous() copies).  srcs / dsts / chans
- * are HOST arrays of device pointers / channel counts; HW % 4 == 0, pointers 16-B aligned. */
+ * are HOST arrays of device pointers / channel counts; HW % 4 == 0, pointers 16-B aligned
+ * (any other is refused with E2EP_EINVAL, nothing launched: nn_ops.cat_channels copies a
+ * misaligned piece or gradient first). */
 int e2ep_cat_channels(const float *const *srcs, const int *chans, int n, int N, long long HW,
                       float *dst, void *stream);
 int e2ep_split_channels(const float *src, const int *chans, int n, int N, long long HW,
@@ -538,7 +540,9 @@ int e2ep_softmax_c_bwd(const float *y, const float *dy, int N, int C, int HW, fl
                        void *stream);
 /* Transformer feed-forward activation y = dropout_p(relu(x)) over n floats (n % 4 == 0,
  * 16-B aligned), and dx = dy * relu'(x) * keep / (1-p).  Keep bit of element c = the
- * attention hash of (*seed, c) (e2ep_attn_keep_mask with BH = Sq = 1, Sk = n shows it). */
+ * attention hash of (*seed, c) (e2ep_attn_keep_mask with BH = Sq = 1, Sk = n shows it).
+ * A pointer off 16-byte alignment is refused (E2EP_EINVAL, nothing launched): the caller copies
+ * such an operand first, as nn_ops.relu_dropout does. */
 int e2ep_relu_dropout_fwd(const float *x, long long n, float p, const int32_t *seed, float *y,
                           void *stream);
 int e2ep_relu_dropout_bwd(const float *x, const float *dy, long long n, float p,
@@ -551,7 +555,13 @@ int e2ep_relu_dropout_bwd(const float *x, const float *dy, long long n, float p,
  * model/convolutions.py:197,238-240.  Backward is a deterministic two-pass gather.
  * ------------------------------------------------------------------------------------- */
 /* forward over N*C planes; plane (n, c) reads x + n*x_nstride + c*Hi*Wi and writes
- * y + n*y_nstride + c*Ho*Wo, so channel slices of larger tensors are read/written in place. */
+ * y + n*y_nstride + c*Ho*Wo, so channel slices of larger tensors are read/written in place.
+ * Placement (pinned by tests/test_strided_entries_gpu.py): x_nstride >= C*Hi*Wi,
+ * y_nstride >= C*Ho*Wo and (backward) g_pstride >= Ho*Wo may exceed those minima; x, y, g and
+ * gx may sit at any 4-byte-aligned address (a 16-byte-aligned y with Wo % 4 == 0 and
+ * y_nstride % 4 == 0 selects 16-byte stores, bitwise the same values).  gx is dense
+ * [planes][Hi*Wi].  What lies between the planes of one image and the next is never read into
+ * a result and never written. */
 int e2ep_resize_fwd(const float *x, int N, int C, long long x_nstride, int Hi, int Wi, int Ho,
                     int Wo, float scale_h, float scale_w, float *y, long long y_nstride,
                     void *stream);
@@ -692,6 +702,13 @@ int e2ep_embed_tokens_bwd(const float *dout, const int64_t *tok, int tok_stride,
  *   + LN_res(res[b])[n] for n < N; bias, res nullable; act = ReLU when relu; the residual's
  *   LayerNorm (res_gamma, res_beta, res_eps) runs over its N values.  out must not alias x or
  *   res.
+ * Placement (pinned by tests/test_strided_entries_gpu.py): every pointer may sit at any
+ * 4-byte-aligned address (seq: 8-byte).  ldx >= E (K), ldkv >= 2E, ldr >= N, ldo >= N and
+ * seq_stride >= T may each exceed that minimum; sample b's keys / values start at
+ * kv + b * Sk * ldkv.  The weights (w_in, w_q, w: rows of E / K floats), table, pos, x0, cache
+ * and the attention entries' out are dense.  Elements of x, kv, res, seq and out between a
+ * row's end and the next row's start are never read into a result and never written; the
+ * strides change no result bit.
  * ------------------------------------------------------------------------------------- */
 int e2ep_dec_self_attn(const float *x, int ldx, const float *gamma, const float *beta, float eps,
                        const float *table, int V, const float *pos, float *x0, const int64_t *seq,
@@ -819,6 +836,18 @@ int e2ep_depth_bce_bwd(const float *prob, const int *cls, const float *den, cons
  *   : B[k*ldb + n];  C row-major with leading dimension ldc.
  * v_mfma_f32_32x32x2_f32, fixed summation order (deterministic).  Small grids split K and
  * need e2ep_gemm_workspace(M, N, K) bytes of workspace (0 when no split).
+ * Placement (e2ep_gemm, e2ep_gemm_rowsum, e2ep_linear_bwd; pinned by
+ * tests/test_gemm_placement_gpu.py): every operand pointer (A, B, bias, Cadd, C, rowsum; dy, x,
+ * w, gskip, dx, dw, db) may sit at any 4-byte-aligned address, and every leading dimension may
+ * exceed its minimum (the row length of that operand), each independently of the others.
+ * Alignment and leading dimensions only select how a k-contiguous operand is loaded (16-, 8- or
+ * 4-byte loads: ld % 4 == 0 and a 16-byte-aligned base, ld % 2 == 0 and an 8-byte-aligned base,
+ * else dwords) and the vector width of the separate split-K reduction; for the MFMA kernels
+ * the result is bitwise the one of dense, aligned copies under the same tile and split
+ * setting.  The few-row kernel (e2ep_gemm_skinny) has two variants that sum in different
+ * orders (lda, ldb even and A, B 8-byte aligned; otherwise): equal within rounding only.
+ * The elements between a row's end and the next row's start (and before / after the operand)
+ * are never read into a result, whatever they hold (NaN included), and never written.
  * ------------------------------------------------------------------------------------- */
 size_t e2ep_gemm_workspace(int M, int N, int K);
 /* Benchmarking override of the launch plan: block tile 1 = 64x64, 2 = 32x128, 3 = 128x128,
