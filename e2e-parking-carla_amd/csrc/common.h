@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "e2ep.h"
 #include "tune.h"
 
@@ -24,6 +26,10 @@ inline int launch_status(const char *what) {
 }
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// Host-side template dispatch: a launcher turns a runtime choice into template arguments by
+// calling a generic lambda with integral constants (constexpr int V = decltype(v)::value).
+template <int V> using IntC = std::integral_constant<int, V>;
 
 // Branch-free guarded memory access.  `if (ok) v = p[i];` inside an unrolled loop makes
 // hipcc branch around every load and wait vmcnt(0) per element, serialising the loads; a

@@ -65,11 +65,8 @@ struct TapList {
   int tap[MAXTAPS];
 };
 
-// Host-side template dispatch: a launcher turns a runtime choice into template arguments by
-// calling a generic lambda with integral constants (constexpr int V = decltype(v)::value).
-template <int V> using IntC = std::integral_constant<int, V>;
-// f(IntC<I>, IntC<J>), I / J = 2 where i2 / j2, else 1: the 2 x 2 tile choices of k_wgrad_1x1
-// (32- / 64-row wave tiles) and k_wgrad_lp (64- / 128-row tiles)
+// f(IntC<I>, IntC<J>) (common.h IntC), I / J = 2 where i2 / j2, else 1: the 2 x 2 tile choices
+// of k_wgrad_1x1 (32- / 64-row wave tiles) and k_wgrad_lp (64- / 128-row tiles)
 template <class F> inline void with_tile2x2(bool i2, bool j2, F f) {
   if (i2 && j2) f(IntC<2>(), IntC<2>());
   else if (i2) f(IntC<2>(), IntC<1>());

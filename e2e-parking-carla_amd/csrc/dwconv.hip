@@ -669,13 +669,6 @@ __global__ void __launch_bounds__(256) k_dw_bwd_pair_s2(const dw_to<B> *__restri
     dw_dgrad_s2_body<K, PLP, B>(gy, w, g, RO, GR, WPg, upp2, units2, dx, b - nw);
 }
 
-static int dw_splits(long long pixels, int C) {
-  long long want = (1024 + C - 1) / C;
-  long long cap = pixels / 2048;
-  long long s = want < cap ? want : cap;
-  return (int)(s < 1 ? 1 : (s > 128 ? 128 : s));
-}
-
 static DwGeom dw_geom(const int *d) {
   DwGeom g;
   g.N = d[0]; g.C = d[1]; g.H = d[2]; g.W = d[3]; g.K = d[4]; g.P = d[5]; g.Q = d[6];
@@ -683,181 +676,81 @@ static DwGeom dw_geom(const int *d) {
   return g;
 }
 
-}  // namespace e2ep
+// ---- launch plan -------------------------------------------------------------------------
+// dw_plan() is the only place that says which kernel runs for a geometry; the launchers, the
+// statistics / pair / storage / workspace queries and the paired backward all read its answer.
 
-using namespace e2ep;
-
-#define DW_DISPATCH(KERNEL, GRID, ...)                                                        \
-  do {                                                                                        \
-    if (g.K == 3 && g.st == 1)                                                                \
-      hipLaunchKernelGGL((KERNEL<3, 1>), GRID, dim3(256), 0, as_stream(stream), __VA_ARGS__); \
-    else if (g.K == 3 && g.st == 2)                                                           \
-      hipLaunchKernelGGL((KERNEL<3, 2>), GRID, dim3(256), 0, as_stream(stream), __VA_ARGS__); \
-    else if (g.K == 5 && g.st == 1)                                                           \
-      hipLaunchKernelGGL((KERNEL<5, 1>), GRID, dim3(256), 0, as_stream(stream), __VA_ARGS__); \
-    else if (g.K == 5 && g.st == 2)                                                           \
-      hipLaunchKernelGGL((KERNEL<5, 2>), GRID, dim3(256), 0, as_stream(stream), __VA_ARGS__); \
-    else {                                                                                    \
-      set_error("depthwise conv: kernel %d / stride %d unsupported (k 3|5, s 1|2)", g.K, g.st); \
-      return E2EP_ERANGE;                                                                     \
-    }                                                                                         \
-  } while (0)
-
-// the strip kernels' LDS row-read variant: dw_row's OFF for left pad pl, or -1 (scalar reads)
 // grid of the forward strip kernel: one unit per wave up to e2ep_tune key 24 blocks
 static int dw_fwd_blocks(int units) { return std::min(cdiv(units, 4), g_tune[TUNE_DW_FWD_BLOCKS]); }
+// the strip kernels' LDS row-read variant: dw_row's OFF for left pad pl, or -1 (scalar reads,
+// e2ep_tune key 23 = 1)
 static int dw_off(int pl) { return g_tune[TUNE_DW_VEC] == 1 ? -1 : ((-pl) & 3); }
 
-// launch a strip kernel with the row-read variant `off` as its compile-time OFF and the
-// staging registers V = 2 float4 per lane when `nv` (float4 per lane a unit needs) allows
-// (the scalar-read variant, an A/B switch, always takes DW_MAXV)
-template <int K, int ST, bool FLIP, int V, bool B>
-static void dw_fwd_strip_v(int off, dim3 grid, size_t shm, hipStream_t st, const void *xv,
-                           const float *w, DwGeom g, DwStrip d, int units, void *yv, DwIn tf,
-                           double *stats) {
-  const auto *x = static_cast<const dw_ti<FLIP, B> *>(xv);
-  auto *y = static_cast<dw_to<B> *>(yv);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), shm, st, x, w, g, d, units, y, tf, stats);
-  };
-  if (stats && !FLIP) {
-    switch (off) {
-      case 0: go(k_dw_fwd_strip<K, ST, FLIP, 0, V, true, B>); break;
-      case 1: go(k_dw_fwd_strip<K, ST, FLIP, 1, V, true, B>); break;
-      case 2: go(k_dw_fwd_strip<K, ST, FLIP, 2, V, true, B>); break;
-      default: go(k_dw_fwd_strip<K, ST, FLIP, 3, V, true, B>);
-    }
-    return;
-  }
-  switch (off) {
-    case 0: go(k_dw_fwd_strip<K, ST, FLIP, 0, V, false, B>); break;
-    case 1: go(k_dw_fwd_strip<K, ST, FLIP, 1, V, false, B>); break;
-    case 2: go(k_dw_fwd_strip<K, ST, FLIP, 2, V, false, B>); break;
-    default: go(k_dw_fwd_strip<K, ST, FLIP, 3, V, false, B>);
-  }
-}
-template <int K, int ST, bool FLIP, bool B>
-static void dw_fwd_strip(int off, int nv, dim3 grid, size_t shm, hipStream_t st, const void *xv,
-                         const float *w, DwGeom g, DwStrip d, int units, void *yv, DwIn tf,
-                         double *stats) {
-  const auto *x = static_cast<const dw_ti<FLIP, B> *>(xv);
-  auto *y = static_cast<dw_to<B> *>(yv);
-  if (off < 0 && stats && !FLIP)
-    hipLaunchKernelGGL((k_dw_fwd_strip<K, ST, FLIP, -1, DW_MAXV, true, B>), grid, dim3(256), shm, st,
-                       x, w, g, d, units, y, tf, stats);
-  else if (off < 0)
-    hipLaunchKernelGGL((k_dw_fwd_strip<K, ST, FLIP, -1, DW_MAXV, false, B>), grid, dim3(256), shm, st,
-                       x, w, g, d, units, y, tf, nullptr);
-  else if (nv <= 2)
-    dw_fwd_strip_v<K, ST, FLIP, 2, B>(off, grid, shm, st, xv, w, g, d, units, yv, tf, stats);
-  else
-    dw_fwd_strip_v<K, ST, FLIP, DW_MAXV, B>(off, grid, shm, st, xv, w, g, d, units, yv, tf, stats);
-}
-template <int K, int ST, int V, bool B>
-static void dw_wgrad_strip_v(int off, dim3 grid, size_t shm, hipStream_t st, const void *gyv,
-                             const float *x, DwGeom g, DwStrip d, int splits, DwPart part, DwIn tf) {
-  const auto *gy = static_cast<const dw_to<B> *>(gyv);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), shm, st, gy, x, g, d, splits, part, tf); };
-  switch (off) {
-    case 0: go(k_dw_wgrad_strip<K, ST, 0, V, B>); break;
-    case 1: go(k_dw_wgrad_strip<K, ST, 1, V, B>); break;
-    case 2: go(k_dw_wgrad_strip<K, ST, 2, V, B>); break;
-    default: go(k_dw_wgrad_strip<K, ST, 3, V, B>);
-  }
-}
-template <int K, int ST, bool B>
-static void dw_wgrad_strip(int off, int nv, dim3 grid, size_t shm, hipStream_t st, const void *gyv,
-                           const float *x, DwGeom g, DwStrip d, int splits, DwPart part, DwIn tf) {
-  if (off < 0)
-    hipLaunchKernelGGL((k_dw_wgrad_strip<K, ST, -1, DW_MAXV, B>), grid, dim3(256), shm, st,
-                       static_cast<const dw_to<B> *>(gyv), x, g, d, splits, part, tf);
-  else if (nv <= 2)
-    dw_wgrad_strip_v<K, ST, 2, B>(off, grid, shm, st, gyv, x, g, d, splits, part, tf);
-  else
-    dw_wgrad_strip_v<K, ST, DW_MAXV, B>(off, grid, shm, st, gyv, x, g, d, splits, part, tf);
-}
+// One geometry on k_dw_fwd_strip / k_dw_wgrad_strip: the unit shape, the forward grid
+// (`blocks`), the dynamic LDS, the row-read variant `off` as the kernels' compile-time OFF and
+// the staging registers V = 2 float4 per lane where a unit's IR * W / 4 float4 allow (the
+// scalar-read variant, an A/B switch, always takes DW_MAXV).
+struct DwRoute {
+  bool ok;
+  DwGeom g;
+  DwStrip d;
+  int units, blocks, off, v;
+  size_t lds;
+};
 
-extern "C" {
-
-static bool dw_strip_ok(const DwGeom &g) {
+// The strip gate.  Shape: Q % 4 == 0 and Q <= 256 (a unit is 64 lanes x 4 outputs), W % 4 == 0
+// (float4 staging), an instantiated (K, stride), and a unit's rows within the unrolled
+// staging's reach (IR * W / 4 <= 64 * DW_MAXV float4).
+// Halo: a staged row holds WP = W + 2 * DW_PADL floats, [0, DW_PADL) and [DW_PADL + W, WP) zero.
+// The lane at output column ox0 (0, 4, .., Q - 4) reads its window row from
+//   base = DW_PADL + ox0 * ST - pl   (dw_fwd_strip_body / dw_wgrad_strip_body),
+// NV = 3 * ST + K floats.  The scalar reads (OFF = -1) touch [base, base + NV): inside [0, WP)
+// for every lane iff
+//   pl <= DW_PADL   and   DW_PADL + (Q - 4) * ST - pl + 3 * ST + K <= WP,
+// the second being "the right pad the output width implies, (Q - 1) * ST + K - pl - W, is at
+// most DW_PADL".  The vector reads (dw_row, OFF = -pl mod 4) touch [base - OFF,
+// base - OFF + 4 * ceil((OFF + NV) / 4)): base - OFF is base rounded down to a multiple of 4
+// (DW_PADL, ox0 * ST and pl + OFF are multiples of 4) and the end is base + NV rounded up to
+// one; 0 and WP are multiples of 4, so the same two inequalities bound the vector reads.  TF
+// "same" pads (at most 2 left, 3 right) always satisfy them; a larger asymmetric pad takes the
+// generic kernels.
+static DwRoute dw_route(const DwGeom &g) {
+  DwRoute r{};
+  r.g = g;
   if (!(g.Q % 4 == 0 && g.Q <= 256 && g.W % 4 == 0 && (g.K == 3 || g.K == 5) &&
         (g.st == 1 || g.st == 2)))
-    return false;
-  const DwStrip d = dw_strip(g.K, g.st, g.W, g.P, g.Q);
-  return d.IR * (g.W / 4) <= 64 * DW_MAXV;  // the unrolled staging's reach
+    return r;
+  r.d = dw_strip(g.K, g.st, g.W, g.P, g.Q);
+  const int nv = r.d.IR * (g.W / 4);  // float4 of a unit's rows
+  if (nv > 64 * DW_MAXV) return r;
+  if (g.pl > DW_PADL || DW_PADL + (g.Q - 4) * g.st - g.pl + 3 * g.st + g.K > r.d.WP) return r;
+  r.ok = true;
+  r.units = g.N * g.C * r.d.units_per_plane;
+  r.blocks = dw_fwd_blocks(r.units);
+  r.off = dw_off(g.pl);
+  r.v = r.off >= 0 && cdiv(nv, 64) <= 2 ? 2 : DW_MAXV;
+  r.lds = 4 * r.d.IR * r.d.WP * sizeof(float);
+  return r;
 }
 
-#define DW_STRIP_DISPATCH(LAUNCHER, FLIPARG, GRID, SHMEM, ...)                                   \
-  do {                                                                                         \
-    const int off = dw_off(g.pl);                                                              \
-    const int nv = cdiv(d.IR * (g.W / 4), 64);                                                 \
-    if (g.K == 3 && g.st == 1)                                                                 \
-      LAUNCHER<3, 1 FLIPARG>(off, nv, GRID, SHMEM, as_stream(stream), __VA_ARGS__);                \
-    else if (g.K == 3 && g.st == 2)                                                            \
-      LAUNCHER<3, 2 FLIPARG>(off, nv, GRID, SHMEM, as_stream(stream), __VA_ARGS__);                \
-    else if (g.K == 5 && g.st == 1)                                                            \
-      LAUNCHER<5, 1 FLIPARG>(off, nv, GRID, SHMEM, as_stream(stream), __VA_ARGS__);                \
-    else                                                                                       \
-      LAUNCHER<5, 2 FLIPARG>(off, nv, GRID, SHMEM, as_stream(stream), __VA_ARGS__);                \
-  } while (0)
-#define DW_NOFLIP , false, false
-#define DW_NOFLIP_B16 , false, true
-#define DW_NONE , false
-#define DW_B16 , true
-
-// dims[10] = {N, C, H, W, K, P, Q, stride, pad_top, pad_left}
-int e2ep_dwconv_fwd_stats_tiles(const int *dims) {
-  const DwGeom g = dw_geom(dims);
-  if (!(g.N > 0 && g.C > 0 && g.P > 0 && g.Q > 0 && g.st > 0) || !dw_strip_ok(g)) return 0;
-  return g.N * dw_strip(g.K, g.st, g.W, g.P, g.Q).units_per_plane;
+// stride 1: dx = gy (P x Q) correlated with the flipped filter, pads K-1-pad, output H x W
+static DwRoute dw_route_flipped(const DwGeom &g) {
+  DwGeom t = g;
+  t.H = g.P; t.W = g.Q; t.P = g.H; t.Q = g.W;
+  t.pt = g.K - 1 - g.pt; t.pl = g.K - 1 - g.pl;
+  if (g.st != 1 || t.pt < 0 || t.pl < 0) return DwRoute{};
+  return dw_route(t);
 }
 
-int e2ep_dwconv_fwd(const float *x, const float *w, const int *dims, const float *in_scale,
-                    const float *in_shift, int in_act, float *y, void *stream) {
-  return e2ep_dwconv_fwd_stats(x, w, dims, in_scale, in_shift, in_act, y, nullptr, 0, stream, 0);
-}
-
-int e2ep_dwconv_fwd_stats(const float *x, const float *w, const int *dims, const float *in_scale,
-                          const float *in_shift, int in_act, void *y, double *stats,
-                          size_t stats_bytes, void *stream, int io) {
-  DwGeom g = dw_geom(dims);
-  E2EP_REQUIRE(io == 0 || (io == E2EP_IO_DX_BF16 && dw_strip_ok(g)), E2EP_EINVAL,
-               "e2ep_dwconv_fwd_stats: storage mask %d not supported (0, or y bf16 on the strip "
-               "kernels)", io);
-  if (stats) {
-    const int tiles = e2ep_dwconv_fwd_stats_tiles(dims);
-    E2EP_REQUIRE(tiles > 0, E2EP_EINVAL,
-                 "e2ep_dwconv_fwd_stats: this geometry's kernel takes no statistics");
-    E2EP_REQUIRE(stats_bytes >= (size_t)g.C * tiles * 2 * sizeof(double), E2EP_EINVAL,
-                 "e2ep_dwconv_fwd_stats: stats %zu bytes < %zu (C x tiles x 2 doubles)",
-                 stats_bytes, (size_t)g.C * tiles * 2 * sizeof(double));
-  }
-  E2EP_REQUIRE(!in_scale == !in_shift && in_act >= 0 && in_act <= 2, E2EP_EINVAL,
-               "e2ep_dwconv_fwd: in_scale / in_shift both or neither, in_act 0..2");
-  const DwIn tf{in_scale, in_shift, in_act};
-  E2EP_REQUIRE(g.N > 0 && g.C > 0 && g.P > 0 && g.Q > 0 && g.st > 0, E2EP_EINVAL,
-               "e2ep_dwconv_fwd: bad geometry");
-  if (dw_strip_ok(g)) {
-    const DwStrip d = dw_strip(g.K, g.st, g.W, g.P, g.Q);
-    const int units = g.N * g.C * d.units_per_plane;
-    if (io)
-      DW_STRIP_DISPATCH(dw_fwd_strip, DW_NOFLIP_B16, dim3(dw_fwd_blocks(units)), 4 * d.IR * d.WP * 4,
-                        x, w, g, d, units, y, tf, stats);
-    else
-      DW_STRIP_DISPATCH(dw_fwd_strip, DW_NOFLIP, dim3(dw_fwd_blocks(units)), 4 * d.IR * d.WP * 4, x,
-                        w, g, d, units, y, tf, stats);
-    return launch_status("e2ep_dwconv_fwd");
-  }
-  E2EP_REQUIRE(g.N * g.C <= 65535, E2EP_ERANGE, "e2ep_dwconv_fwd: N*C > 65535");
-  DW_DISPATCH(k_dw_fwd, dim3(cdiv(g.P * g.Q, 256), g.N * g.C), x, w, g, static_cast<float *>(y),
-              in_scale, in_shift, in_act);
-  return launch_status("e2ep_dwconv_fwd");
-}
-
-// The stride-2 data-gradient strip plan of e2ep_dwconv_dgrad (RO output rows per unit, GR gy
-// rows staged); false where that entry point runs the generic kernel.
+// The stride-2 data-gradient strip plan (RO dx rows per unit, GR gy rows staged, one unit per
+// wave); false where the data gradient runs the generic kernel.
+// Halo: a staged gy row holds WPg = Q + 2 * DW_PADL floats.  The lane at dx column ix0 (0, 4,
+// .., W - 4) reads column DW_PADL + ix0 / 2 + (pl - PLP) / 2 + (u + PLP - b) / 2 for u < 4 and
+// the taps b < K with u + PLP - b even (dw_dgrad_s2_body): lowest at ix0 = 0, u = 0 and the
+// largest such b (K - 1 - PLP), highest at ix0 = W - 4, u = 3 and the smallest (1 - PLP).
 struct DwS2 {
-  int RO, GR, WPg, upp, units;
+  int RO, GR, WPg, upp, units, blocks;
+  size_t lds;
 };
 static bool dw_s2_plan(const DwGeom &g, DwS2 &p) {
   if (!(g.st == 2 && g.W % 4 == 0 && g.W <= 256 && g.Q % 4 == 0 && (g.K == 3 || g.K == 5) &&
@@ -867,265 +760,359 @@ static bool dw_s2_plan(const DwGeom &g, DwS2 &p) {
   p.GR = ((p.RO - 1 + g.pt) >> 1) - ((g.pt - (g.K - 1)) >> 1) + 2;
   if (p.GR * (g.Q / 4) > 64 * DW_MAXV) return false;
   p.WPg = g.Q + 2 * DW_PADL;
+  const int plp = g.pl & 1, x0 = DW_PADL + ((g.pl - plp) >> 1);
+  if (x0 - ((g.K - 1 - plp) >> 1) < 0 || x0 + (g.W - 4) / 2 + 1 + plp >= p.WPg) return false;
   p.upp = (g.H + p.RO - 1) / p.RO;
   p.units = g.N * g.C * p.upp;
+  p.blocks = cdiv(p.units, 4);
+  p.lds = 4 * p.GR * p.WPg * sizeof(float);
   return true;
+}
+
+// Not for stride-2 data gradients of more than DW_S2_PAIR_UNITS units: the 128 x 128-map layer
+// (294 912 units) ran 220 us paired against ~183 us as two forked launches, while the 43 008-
+// and 98 304-unit layers ran 37 / 87 us paired against ~44 / ~86 us forked
+// (step_sequence_fp32_final.txt against _r4z.txt).
+constexpr int DW_S2_PAIR_UNITS = 131072;
+
+enum DwKind { DW_GENERIC, DW_STRIP, DW_STRIP_S2 };
+enum DwPair { DW_PAIR_NONE, DW_PAIR_S1, DW_PAIR_S2 };
+struct DwPlan {
+  bool valid;        // N, C, P, Q, stride > 0; nothing below is set otherwise
+  DwGeom g;
+  int fwd, wgrad;    // DW_STRIP: k_dw_fwd_strip / k_dw_wgrad_strip on route s; else k_dw_fwd / k_dw_wgrad
+  int dgrad;         // DW_STRIP: k_dw_fwd_strip<FLIP> on route t (stride 1); DW_STRIP_S2:
+                     // k_dw_dgrad_s2_strip on s2; else k_dw_dgrad
+  DwRoute s, t;
+  DwS2 s2;
+  int stats_tiles;   // units per channel: the forward's BatchNorm partial sums, 0 = not taken
+  int splits;        // weight-gradient slabs
+  size_t workspace;  // bytes of the slabs
+  int pair;          // e2ep_dwconv_bwd: both gradients in k_dw_bwd_pair (S1) / k_dw_bwd_pair_s2 (S2)
+  int fwd_io, dgrad_io, wgrad_io;  // E2EP_IO_* storage mask each direction accepts besides 0
+  bool bf16_ok;      // every kernel of the layer, and the BatchNorms beside it, take bf16 storage
+};
+
+// Gates in order.  Forward and weight gradient: the strip kernels where dw_route(g), else the
+// generic ones.  Data gradient: the flipped strip forward (stride 1, dw_route of the flipped
+// geometry), the stride-2 strip kernel (dw_s2_plan), else the generic one.  Paired backward:
+// both halves on strip kernels with vector row reads at an instantiated combination:
+// stride 1 with one OFF for both halves (symmetric padding, K = 3 pad 1 -> 3, K = 5 pad 2 -> 2);
+// stride 2 at K = 3 pad_left 0 / 1, K = 5 pad_left 1 / 2, up to DW_S2_PAIR_UNITS units.
+static DwPlan dw_plan(const DwGeom &g) {
+  DwPlan p{};
+  p.g = g;
+  p.valid = g.N > 0 && g.C > 0 && g.P > 0 && g.Q > 0 && g.st > 0;
+  if (!p.valid) return p;
+  p.s = dw_route(g);
+  p.t = dw_route_flipped(g);
+  if (p.s.ok) {
+    p.fwd = p.wgrad = DW_STRIP;
+    p.stats_tiles = g.N * p.s.d.units_per_plane;
+    p.fwd_io = E2EP_IO_DX_BF16;
+    p.wgrad_io = E2EP_IO_DY_BF16;
+  }
+  p.dgrad = p.t.ok ? DW_STRIP : dw_s2_plan(g, p.s2) ? DW_STRIP_S2 : DW_GENERIC;
+  if (p.dgrad != DW_GENERIC) p.dgrad_io = E2EP_IO_DY_BF16 | E2EP_IO_DX_BF16;
+  // slabs: e2ep_tune key 3 workgroups (generic kernel: 1024) over the C channels, each split
+  // of >= 8 units, 2 per wave (generic: >= 2048 pixels); 1 .. 128
+  const bool ws = p.wgrad == DW_STRIP;
+  const long long want = cdiv(ws ? g_tune[TUNE_DW_WGRAD_TARGET] : 1024, g.C);
+  const long long cap = ws ? (p.stats_tiles + 7) / 8 : (long long)g.N * g.P * g.Q / 2048;
+  p.splits = (int)std::max(1LL, std::min({want, cap, 128LL}));
+  p.workspace = (size_t)g.C * p.splits * g.K * g.K * sizeof(float);
+  if (p.wgrad == DW_STRIP && p.s.off >= 0) {
+    if (p.dgrad == DW_STRIP && p.t.off == p.s.off && p.s.off == (g.K == 3 ? 3 : 2))
+      p.pair = DW_PAIR_S1;
+    else if (p.dgrad == DW_STRIP_S2 && p.s2.units <= DW_S2_PAIR_UNITS &&
+             (g.K == 3 ? g.pl == 0 || g.pl == 1 : g.pl == 1 || g.pl == 2))
+      p.pair = DW_PAIR_S2;
+  }
+  p.bf16_ok = p.fwd == DW_STRIP && p.dgrad != DW_GENERIC && (g.H * g.W) % 4 == 0 &&
+              (g.P * g.Q) % 4 == 0;
+  return p;
+}
+
+// ---- template dispatch: f is a generic lambda taking integral constants (common.h IntC) -----
+// f(K, ST) for the instantiated filters and strides; E2EP_ERANGE for any other
+template <class F> static int with_k_st(const DwGeom &g, F f) {
+  if (g.K == 3 && g.st == 1) f(IntC<3>(), IntC<1>());
+  else if (g.K == 3 && g.st == 2) f(IntC<3>(), IntC<2>());
+  else if (g.K == 5 && g.st == 1) f(IntC<5>(), IntC<1>());
+  else if (g.K == 5 && g.st == 2) f(IntC<5>(), IntC<2>());
+  else {
+    set_error("depthwise conv: kernel %d / stride %d unsupported (k 3|5, s 1|2)", g.K, g.st);
+    return E2EP_ERANGE;
+  }
+  return 0;
+}
+// f(K), K = 3 or 5 (the strip routes have no other)
+template <class F> static void with_k(int K, F f) {
+  if (K == 3) f(IntC<3>());
+  else f(IntC<5>());
+}
+// f(0 / 1) for a two-way choice (bf16 storage, statistics, pad parity)
+template <class F> static void with_flag(bool on, F f) {
+  if (on) f(IntC<1>());
+  else f(IntC<0>());
+}
+// f(V), V = 2 or DW_MAXV staging registers
+template <class F> static void with_v(int v, F f) {
+  if (v == 2) f(IntC<2>());
+  else f(IntC<DW_MAXV>());
+}
+// f(OFF, V) of a DwRoute: OFF = -1 exists only with V = DW_MAXV
+template <class F> static void with_off_v(const DwRoute &r, F f) {
+  if (r.off < 0) return f(IntC<-1>(), IntC<DW_MAXV>());
+  with_v(r.v, [&](auto v) {
+    if (r.off == 0) f(IntC<0>(), v);
+    else if (r.off == 1) f(IntC<1>(), v);
+    else if (r.off == 2) f(IntC<2>(), v);
+    else f(IntC<3>(), v);
+  });
+}
+
+// k_dw_fwd_strip on route r: the forward (statistics where `stats`), or with FLIP the
+// stride-1 data gradient, which takes none (no <FLIP, BS> kernel exists)
+template <bool FLIP>
+static void dw_launch_fwd_strip(const DwRoute &r, bool b16, const void *x, const float *w, void *y,
+                                DwIn tf, double *stats, hipStream_t s) {
+  with_k_st(r.g, [&](auto k, auto st) {
+    with_off_v(r, [&](auto off, auto v) {
+      with_flag(b16, [&](auto b) {
+        with_flag(stats != nullptr, [&](auto bs) {
+          constexpr int K = decltype(k)::value, ST = decltype(st)::value;
+          constexpr bool B = decltype(b)::value != 0, BS = decltype(bs)::value != 0;
+          if constexpr (!FLIP || (ST == 1 && !BS))
+            hipLaunchKernelGGL((k_dw_fwd_strip<K, ST, FLIP, decltype(off)::value, decltype(v)::value, BS, B>),
+                               dim3(r.blocks), dim3(256), r.lds, s,
+                               static_cast<const dw_ti<FLIP, B> *>(x), w, r.g, r.d, r.units,
+                               static_cast<dw_to<B> *>(y), tf, stats);
+        });
+      });
+    });
+  });
+}
+
+static void dw_launch_dgrad_s2(const DwPlan &p, bool b16, const void *gy, const float *w, void *dx,
+                               hipStream_t s) {
+  const DwS2 &q = p.s2;
+  with_k(p.g.K, [&](auto k) {
+    with_flag(p.g.pl & 1, [&](auto plp) {
+      with_flag(b16, [&](auto b) {
+        constexpr bool B = decltype(b)::value != 0;
+        hipLaunchKernelGGL((k_dw_dgrad_s2_strip<decltype(k)::value, decltype(plp)::value, B>),
+                           dim3(q.blocks), dim3(256), q.lds, s, static_cast<const dw_to<B> *>(gy), w,
+                           p.g, q.RO, q.GR, q.WPg, q.upp, q.units, static_cast<dw_to<B> *>(dx));
+      });
+    });
+  });
+}
+
+static void dw_launch_wgrad_strip(const DwPlan &p, bool b16, const void *gy, const float *x,
+                                  DwPart part, DwIn tf, hipStream_t s) {
+  const DwRoute &r = p.s;
+  with_k_st(r.g, [&](auto k, auto st) {
+    with_off_v(r, [&](auto off, auto v) {
+      with_flag(b16, [&](auto b) {
+        constexpr bool B = decltype(b)::value != 0;
+        hipLaunchKernelGGL((k_dw_wgrad_strip<decltype(k)::value, decltype(st)::value,
+                                             decltype(off)::value, decltype(v)::value, B>),
+                           dim3(r.g.C, p.splits), dim3(256), r.lds, s,
+                           static_cast<const dw_to<B> *>(gy), x, r.g, r.d, p.splits, part, tf);
+      });
+    });
+  });
+}
+
+// k_dw_bwd_pair: the weight-gradient blocks, then the data-gradient blocks of route t
+static void dw_launch_pair_s1(const DwPlan &p, bool b16, const void *gy, const float *x,
+                              const float *w, void *dx, DwPart part, DwIn tf, hipStream_t s) {
+  const DwRoute &r = p.s, &t = p.t;
+  with_k(p.g.K, [&](auto k) {
+    with_v(t.v, [&](auto vd) {
+      with_v(r.v, [&](auto vw) {
+        with_flag(b16, [&](auto b) {
+          constexpr int K = decltype(k)::value, OFF = K == 3 ? 3 : 2;
+          constexpr bool B = decltype(b)::value != 0;
+          hipLaunchKernelGGL((k_dw_bwd_pair<K, OFF, decltype(vd)::value, decltype(vw)::value, B>),
+                             dim3(t.blocks + r.g.C * p.splits), dim3(256), std::max(t.lds, r.lds), s,
+                             static_cast<const dw_to<B> *>(gy), w, t.g, t.d, t.units,
+                             static_cast<dw_to<B> *>(dx), t.blocks, x, r.g, r.d, p.splits, part, tf);
+        });
+      });
+    });
+  });
+}
+
+// k_dw_bwd_pair_s2: PLP = pad_left & 1, OFF = -pad_left mod 4 (dw_off) of the four instantiated
+// (K, pad_left): K = 3 pad 0 / 1 -> OFF 0 / 3, K = 5 pad 1 / 2 -> OFF 3 / 2
+static void dw_launch_pair_s2(const DwPlan &p, bool b16, const void *gy, const float *x,
+                              const float *w, void *dx, DwPart part, DwIn tf, hipStream_t s) {
+  const DwRoute &r = p.s;
+  const DwS2 &q = p.s2;
+  with_k(p.g.K, [&](auto k) {
+    with_flag(p.g.pl & 1, [&](auto plp) {
+      with_v(r.v, [&](auto vw) {
+        with_flag(b16, [&](auto b) {
+          constexpr int K = decltype(k)::value, PLP = decltype(plp)::value;
+          constexpr int OFF = PLP ? 3 : K == 3 ? 0 : 2;
+          constexpr bool B = decltype(b)::value != 0;
+          hipLaunchKernelGGL((k_dw_bwd_pair_s2<K, PLP, OFF, decltype(vw)::value, B>),
+                             dim3(r.g.C * p.splits + q.blocks), dim3(256), std::max(q.lds, r.lds), s,
+                             static_cast<const dw_to<B> *>(gy), w, q.RO, q.GR, q.WPg, q.upp, q.units,
+                             static_cast<dw_to<B> *>(dx), x, r.g, r.d, p.splits, part, tf);
+        });
+      });
+    });
+  });
+}
+
+// one split: the slab is the gradient; several: in-launch fold (e2ep_tune key 28 = 2) or
+// k_dw_wgrad_finalize after the launch (dw_finalize)
+static DwPart dw_part(const DwPlan &p, void *workspace, float *dw, hipStream_t s) {
+  return DwPart{static_cast<float *>(workspace), dw,
+                (p.splits > 1 && g_tune[TUNE_SPLITK_FOLD] == 2) ? handoff_slots(p.g.C, s) : nullptr};
+}
+static void dw_finalize(const DwPlan &p, const DwPart &part, hipStream_t s) {
+  const int KK = p.g.K * p.g.K;
+  if (p.splits > 1 && !part.cnt)
+    hipLaunchKernelGGL(k_dw_wgrad_finalize, dim3(cdiv(p.g.C * KK, 256)), dim3(256), 0, s, part.part,
+                       p.g.C, KK, p.splits, part.dw);
+}
+
+// What the launch entry points require, in one place (0, or the status to hand back): a
+// geometry; a storage mask that is 0 or the one (io_ok) the planned kernel takes; an input
+// transform with both vectors or neither; where need_ws, the weight gradient's slabs.
+static int dw_check(const char *fn, const DwPlan &p, int io, int io_ok,
+                    DwIn tf = DwIn{nullptr, nullptr, 0}, bool need_ws = false,
+                    const void *workspace = nullptr, size_t workspace_bytes = 0) {
+  E2EP_REQUIRE(p.valid, E2EP_EINVAL, "%s: bad geometry", fn);
+  E2EP_REQUIRE(io == 0 || io == io_ok, E2EP_EINVAL, "%s: storage mask %d not supported (0, or %d "
+               "(E2EP_IO_*) where the strip kernels run)", fn, io, io_ok);
+  E2EP_REQUIRE(!tf.sc == !tf.sh && tf.act >= 0 && tf.act <= 2, E2EP_EINVAL,
+               "%s: in_scale / in_shift both or neither, in_act 0..2", fn);
+  E2EP_REQUIRE(!need_ws || (workspace && workspace_bytes >= p.workspace), E2EP_EINVAL,
+               "%s: workspace %zu bytes < %zu (e2ep_dwconv_wgrad_workspace)", fn, workspace_bytes,
+               p.workspace);
+  return 0;
+}
+
+}  // namespace e2ep
+
+using namespace e2ep;
+
+extern "C" {
+
+// dims[10] = {N, C, H, W, K, P, Q, stride, pad_top, pad_left}
+int e2ep_dwconv_fwd_stats_tiles(const int *dims) { return dw_plan(dw_geom(dims)).stats_tiles; }
+
+int e2ep_dwconv_bwd_pair_ok(const int *dims) {
+  return dw_plan(dw_geom(dims)).pair != DW_PAIR_NONE ? 1 : 0;
+}
+
+int e2ep_dwconv_bf16_ok(const int *dims) { return dw_plan(dw_geom(dims)).bf16_ok ? 1 : 0; }
+
+size_t e2ep_dwconv_wgrad_workspace(const int *dims) { return dw_plan(dw_geom(dims)).workspace; }
+
+int e2ep_dwconv_fwd(const float *x, const float *w, const int *dims, const float *in_scale,
+                    const float *in_shift, int in_act, float *y, void *stream) {
+  return e2ep_dwconv_fwd_stats(x, w, dims, in_scale, in_shift, in_act, y, nullptr, 0, stream, 0);
+}
+
+int e2ep_dwconv_fwd_stats(const float *x, const float *w, const int *dims, const float *in_scale,
+                          const float *in_shift, int in_act, void *y, double *stats,
+                          size_t stats_bytes, void *stream, int io) {
+  const char *fn = "e2ep_dwconv_fwd_stats";
+  const DwPlan p = dw_plan(dw_geom(dims));
+  const DwGeom &g = p.g;
+  const DwIn tf{in_scale, in_shift, in_act};
+  if (int e = dw_check(fn, p, io, p.fwd_io, tf)) return e;
+  if (stats) {
+    E2EP_REQUIRE(p.stats_tiles > 0, E2EP_EINVAL, "%s: this geometry's kernel takes no statistics", fn);
+    const size_t need = (size_t)g.C * p.stats_tiles * 2 * sizeof(double);
+    E2EP_REQUIRE(stats_bytes >= need, E2EP_EINVAL, "%s: stats %zu bytes < %zu (C x tiles x 2 doubles)",
+                 fn, stats_bytes, need);
+  }
+  hipStream_t s = as_stream(stream);
+  if (p.fwd == DW_STRIP) {
+    dw_launch_fwd_strip<false>(p.s, io != 0, x, w, y, tf, stats, s);
+    return launch_status(fn);
+  }
+  E2EP_REQUIRE(g.N * g.C <= 65535, E2EP_ERANGE, "%s: N*C > 65535", fn);
+  const int e = with_k_st(g, [&](auto k, auto st) {
+    hipLaunchKernelGGL((k_dw_fwd<decltype(k)::value, decltype(st)::value>),
+                       dim3(cdiv(g.P * g.Q, 256), g.N * g.C), dim3(256), 0, s, x, w, g,
+                       static_cast<float *>(y), in_scale, in_shift, in_act);
+  });
+  return e ? e : launch_status(fn);
 }
 
 int e2ep_dwconv_dgrad(const void *gy, const float *w, const int *dims, void *dx, void *stream,
                       int io) {
-  DwGeom g = dw_geom(dims);
-  E2EP_REQUIRE(g.N > 0 && g.C > 0 && g.P > 0 && g.Q > 0 && g.st > 0, E2EP_EINVAL,
-               "e2ep_dwconv_dgrad: bad geometry");
-  E2EP_REQUIRE(io == 0 || io == (E2EP_IO_DY_BF16 | E2EP_IO_DX_BF16), E2EP_EINVAL,
-               "e2ep_dwconv_dgrad: storage mask %d not supported (0 or DY|DX bf16)", io);
-  if (g.st == 1) {
-    // stride 1: dx = gy (P x Q) correlated with the flipped filter, pads K-1-pad, output H x W
-    DwGeom t = g;
-    t.H = g.P; t.W = g.Q; t.P = g.H; t.Q = g.W;
-    t.pt = g.K - 1 - g.pt; t.pl = g.K - 1 - g.pl;
-    if (dw_strip_ok(t) && t.pt >= 0 && t.pl >= 0 && t.pl <= DW_PADL) {
-      const DwStrip d = dw_strip(t.K, 1, t.W, t.P, t.Q);
-      const int units = t.N * t.C * d.units_per_plane;
-      const size_t shm = 4 * d.IR * d.WP * 4;
-      const DwIn none{nullptr, nullptr, 0};
-      const int nv = cdiv(d.IR * (t.W / 4), 64);
-      const dim3 grid(dw_fwd_blocks(units));
-      hipStream_t s = as_stream(stream);
-      if (t.K == 3 && io)
-        dw_fwd_strip<3, 1, true, true>(dw_off(t.pl), nv, grid, shm, s, gy, w, t, d, units, dx, none, nullptr);
-      else if (t.K == 3)
-        dw_fwd_strip<3, 1, true, false>(dw_off(t.pl), nv, grid, shm, s, gy, w, t, d, units, dx, none, nullptr);
-      else if (io)
-        dw_fwd_strip<5, 1, true, true>(dw_off(t.pl), nv, grid, shm, s, gy, w, t, d, units, dx, none, nullptr);
-      else
-        dw_fwd_strip<5, 1, true, false>(dw_off(t.pl), nv, grid, shm, s, gy, w, t, d, units, dx, none, nullptr);
-      return launch_status("e2ep_dwconv_dgrad");
-    }
+  const char *fn = "e2ep_dwconv_dgrad";
+  const DwPlan p = dw_plan(dw_geom(dims));
+  const DwGeom &g = p.g;
+  if (int e = dw_check(fn, p, io, p.dgrad_io)) return e;
+  hipStream_t s = as_stream(stream);
+  if (p.dgrad == DW_STRIP) {
+    dw_launch_fwd_strip<true>(p.t, io != 0, gy, w, dx, DwIn{nullptr, nullptr, 0}, nullptr, s);
+    return launch_status(fn);
   }
-  DwS2 p2;
-  if (dw_s2_plan(g, p2)) {
-    const int RO = p2.RO, GR = p2.GR, WPg = p2.WPg, upp = p2.upp, units = p2.units;
-    const size_t shm = 4 * GR * WPg * sizeof(float);
-    const dim3 grid(cdiv(units, 4));
-    const bool odd = g.pl & 1;
-#define DWS2(KV, PV, BV)                                                                           \
-  hipLaunchKernelGGL((k_dw_dgrad_s2_strip<KV, PV, BV>), grid, dim3(256), shm, as_stream(stream),      \
-                     static_cast<const dw_to<BV> *>(gy), w, g, RO, GR, WPg, upp, units,             \
-                     static_cast<dw_to<BV> *>(dx))
-    if (g.K == 3 && !odd) { if (io) DWS2(3, 0, true); else DWS2(3, 0, false); }
-    else if (g.K == 3) { if (io) DWS2(3, 1, true); else DWS2(3, 1, false); }
-    else if (!odd) { if (io) DWS2(5, 0, true); else DWS2(5, 0, false); }
-    else { if (io) DWS2(5, 1, true); else DWS2(5, 1, false); }
-#undef DWS2
-    return launch_status("e2ep_dwconv_dgrad");
+  if (p.dgrad == DW_STRIP_S2) {
+    dw_launch_dgrad_s2(p, io != 0, gy, w, dx, s);
+    return launch_status(fn);
   }
-  E2EP_REQUIRE(io == 0, E2EP_EINVAL, "e2ep_dwconv_dgrad: bf16 storage needs the strip kernels");
-  E2EP_REQUIRE(g.N * g.C <= 65535, E2EP_ERANGE, "e2ep_dwconv_dgrad: N*C > 65535");
-  DW_DISPATCH(k_dw_dgrad, dim3(cdiv(g.H * g.W, 256), g.N * g.C), static_cast<const float *>(gy), w, g,
-              static_cast<float *>(dx));
-  return launch_status("e2ep_dwconv_dgrad");
-}
-
-// the pipelined weight-gradient strip kernel holds a unit's input rows in registers
-static bool dw_wgrad_strip_ok(const DwGeom &g) {
-  if (!dw_strip_ok(g)) return false;
-  const DwStrip d = dw_strip(g.K, g.st, g.W, g.P, g.Q);
-  return d.IR * (g.W / 4) <= 64 * DW_MAXV;
-}
-
-static int dw_wgrad_splits(const DwGeom &g) {
-  if (dw_wgrad_strip_ok(g)) {
-    const DwStrip d = dw_strip(g.K, g.st, g.W, g.P, g.Q);
-    const int cunits = g.N * d.units_per_plane;
-    int want = (g_tune[TUNE_DW_WGRAD_TARGET] + g.C - 1) / g.C;  // e2ep_tune key 3 / 5
-    int cap = (cunits + 7) / 8;                   // >= 8 units (2 per wave) each
-    int s = want < cap ? want : cap;
-    return s < 1 ? 1 : (s > 128 ? 128 : s);
-  }
-  return dw_splits((long long)g.N * g.P * g.Q, g.C);
-}
-
-// The stride-2 paired backward's plan: both strip kernels, weight-gradient row reads at an
-// instantiated (K, pad_left): K = 3 pad 0 / 1, K = 5 pad 1 / 2.  Not for data gradients of
-// more than DW_S2_PAIR_UNITS units: the 128 x 128-map layer (294 912 units) ran 220 us paired
-// against ~183 us as two forked launches, while the 43 008- and 98 304-unit layers ran 37 / 87
-// us paired against ~44 / ~86 us forked (step_sequence_fp32_final.txt against _r4z.txt).
-constexpr int DW_S2_PAIR_UNITS = 131072;
-static bool dw_bwd_pair_s2_plan(const DwGeom &g, DwS2 &p) {
-  if (g.st != 2 || g_tune[TUNE_DW_VEC] == 1 || !dw_wgrad_strip_ok(g) || !dw_s2_plan(g, p) ||
-      p.units > DW_S2_PAIR_UNITS)
-    return false;
-  return (g.K == 3 && (g.pl == 0 || g.pl == 1)) || (g.K == 5 && (g.pl == 1 || g.pl == 2));
-}
-
-// The paired backward's plan (stride 1, both strip kernels, vector row reads with one OFF for
-// both halves: symmetric padding, K = 3 pad 1 -> 3, K = 5 pad 2 -> 2).
-static bool dw_bwd_pair_plan(const DwGeom &g, DwGeom &t, int &off) {
-  if (g.st != 1 || g_tune[TUNE_DW_VEC] == 1 || !dw_wgrad_strip_ok(g)) return false;
-  t = g;
-  t.H = g.P; t.W = g.Q; t.P = g.H; t.Q = g.W;
-  t.pt = g.K - 1 - g.pt; t.pl = g.K - 1 - g.pl;
-  if (!(dw_strip_ok(t) && t.pt >= 0 && t.pl >= 0 && t.pl <= DW_PADL)) return false;
-  off = dw_off(g.pl);
-  return off == dw_off(t.pl) && ((g.K == 3 && off == 3) || (g.K == 5 && off == 2));
-}
-
-int e2ep_dwconv_bwd_pair_ok(const int *dims) {
-  const DwGeom g = dw_geom(dims);
-  DwGeom t;
-  int off;
-  DwS2 p2;
-  return (g.N > 0 && g.C > 0 && g.P > 0 && g.Q > 0 && g.st > 0 &&
-          (dw_bwd_pair_plan(g, t, off) || dw_bwd_pair_s2_plan(g, p2))) ? 1 : 0;
-}
-
-int e2ep_dwconv_bf16_ok(const int *dims) {
-  const DwGeom g = dw_geom(dims);
-  if (!(g.N > 0 && g.C > 0 && g.P > 0 && g.Q > 0 && g.st > 0)) return 0;
-  if (!dw_strip_ok(g) || !dw_wgrad_strip_ok(g)) return 0;  // forward y, weight-gradient gy
-  if ((g.H * g.W) % 4 != 0 || (g.P * g.Q) % 4 != 0) return 0;  // the BatchNorms beside it
-  if (g.st == 1) {  // the stride-1 data gradient's strip path (e2ep_dwconv_dgrad)
-    DwGeom t = g;
-    t.H = g.P; t.W = g.Q; t.P = g.H; t.Q = g.W;
-    t.pt = g.K - 1 - g.pt; t.pl = g.K - 1 - g.pl;
-    return (dw_strip_ok(t) && t.pt >= 0 && t.pl >= 0 && t.pl <= DW_PADL) ? 1 : 0;
-  }
-  DwS2 p2;
-  return dw_s2_plan(g, p2) ? 1 : 0;  // the stride-2 data gradient's strip path
-}
-
-size_t e2ep_dwconv_wgrad_workspace(const int *dims) {
-  DwGeom g = dw_geom(dims);
-  return (size_t)g.C * dw_wgrad_splits(g) * g.K * g.K * sizeof(float);
+  E2EP_REQUIRE(g.N * g.C <= 65535, E2EP_ERANGE, "%s: N*C > 65535", fn);
+  const int e = with_k_st(g, [&](auto k, auto st) {
+    hipLaunchKernelGGL((k_dw_dgrad<decltype(k)::value, decltype(st)::value>),
+                       dim3(cdiv(g.H * g.W, 256), g.N * g.C), dim3(256), 0, s,
+                       static_cast<const float *>(gy), w, g, static_cast<float *>(dx));
+  });
+  return e ? e : launch_status(fn);
 }
 
 int e2ep_dwconv_wgrad(const void *gy, const float *x, const int *dims, const float *in_scale,
                       const float *in_shift, int in_act, void *workspace, size_t workspace_bytes,
                       float *dw, void *stream, int io) {
-  DwGeom g = dw_geom(dims);
-  E2EP_REQUIRE(io == 0 || (io == E2EP_IO_DY_BF16 && dw_wgrad_strip_ok(g)), E2EP_EINVAL,
-               "e2ep_dwconv_wgrad: storage mask %d not supported (0, or gy bf16 on the strip "
-               "kernels)", io);
-  E2EP_REQUIRE(workspace && workspace_bytes >= e2ep_dwconv_wgrad_workspace(dims), E2EP_EINVAL,
-               "e2ep_dwconv_wgrad: workspace %zu bytes < %zu (e2ep_dwconv_wgrad_workspace)",
-               workspace_bytes, e2ep_dwconv_wgrad_workspace(dims));
-  E2EP_REQUIRE(!in_scale == !in_shift && in_act >= 0 && in_act <= 2, E2EP_EINVAL,
-               "e2ep_dwconv_wgrad: in_scale / in_shift both or neither, in_act 0..2");
+  const char *fn = "e2ep_dwconv_wgrad";
+  const DwPlan p = dw_plan(dw_geom(dims));
+  const DwGeom &g = p.g;
   const DwIn tf{in_scale, in_shift, in_act};
-  E2EP_REQUIRE(g.N > 0 && g.C > 0 && g.P > 0 && g.Q > 0 && g.st > 0, E2EP_EINVAL,
-               "e2ep_dwconv_wgrad: bad geometry");
-  const int sp = dw_wgrad_splits(g);
-  // one split: the slab is the gradient; several: in-launch fold or k_dw_wgrad_finalize
-  DwPart part{static_cast<float *>(workspace), dw,
-              (sp > 1 && g_tune[TUNE_SPLITK_FOLD] == 2) ? handoff_slots(g.C, as_stream(stream)) : nullptr};
-  if (dw_wgrad_strip_ok(g)) {
-    const DwStrip d = dw_strip(g.K, g.st, g.W, g.P, g.Q);
-    if (io)
-      DW_STRIP_DISPATCH(dw_wgrad_strip, DW_B16, dim3(g.C, sp), 4 * d.IR * d.WP * 4, gy, x, g, d, sp,
-                        part, tf);
-    else
-      DW_STRIP_DISPATCH(dw_wgrad_strip, DW_NONE, dim3(g.C, sp), 4 * d.IR * d.WP * 4, gy, x, g, d,
-                        sp, part, tf);
+  if (int e = dw_check(fn, p, io, p.wgrad_io, tf, true, workspace, workspace_bytes)) return e;
+  hipStream_t s = as_stream(stream);
+  const DwPart part = dw_part(p, workspace, dw, s);
+  if (p.wgrad == DW_STRIP) {
+    dw_launch_wgrad_strip(p, io != 0, gy, x, part, tf, s);
   } else {
-    DW_DISPATCH(k_dw_wgrad, dim3(g.C, sp), static_cast<const float *>(gy), x, g, sp, part, in_scale,
-                in_shift, in_act);
+    const int e = with_k_st(g, [&](auto k, auto st) {
+      hipLaunchKernelGGL((k_dw_wgrad<decltype(k)::value, decltype(st)::value>), dim3(g.C, p.splits),
+                         dim3(256), 0, s, static_cast<const float *>(gy), x, g, p.splits, part,
+                         in_scale, in_shift, in_act);
+    });
+    if (e) return e;
   }
-  if (sp > 1 && !part.cnt)
-    hipLaunchKernelGGL(k_dw_wgrad_finalize, dim3(cdiv(g.C * g.K * g.K, 256)), dim3(256), 0,
-                       as_stream(stream), part.part, g.C, g.K * g.K, sp, dw);
-  return launch_status("e2ep_dwconv_wgrad");
+  dw_finalize(p, part, s);
+  return launch_status(fn);
 }
 
 int e2ep_dwconv_bwd(const void *gy, const float *x, const float *w, const int *dims,
                     const float *in_scale, const float *in_shift, int in_act, void *dx,
                     void *workspace, size_t workspace_bytes, float *dw, void *stream, int io) {
-  E2EP_REQUIRE(io == 0 || io == (E2EP_IO_DY_BF16 | E2EP_IO_DX_BF16), E2EP_EINVAL,
-               "e2ep_dwconv_bwd: storage mask %d not supported (0 or DY|DX bf16)", io);
-  const bool hb = io != 0;
-  const DwGeom g = dw_geom(dims);
-  DwGeom t;
-  int off;
-  DwS2 p2;
-  const bool geo = g.N > 0 && g.C > 0 && g.P > 0 && g.Q > 0 && g.st > 0;
-  const bool s1 = geo && dw_bwd_pair_plan(g, t, off), s2 = geo && !s1 && dw_bwd_pair_s2_plan(g, p2);
-  E2EP_REQUIRE(s1 || s2, E2EP_EINVAL, "e2ep_dwconv_bwd: no paired backward for this geometry "
-               "(e2ep_dwconv_bwd_pair_ok returned 0)");
-  E2EP_REQUIRE(workspace && workspace_bytes >= e2ep_dwconv_wgrad_workspace(dims), E2EP_EINVAL,
-               "e2ep_dwconv_bwd: workspace %zu bytes < %zu (e2ep_dwconv_wgrad_workspace)",
-               workspace_bytes, e2ep_dwconv_wgrad_workspace(dims));
-  E2EP_REQUIRE(!in_scale == !in_shift && in_act >= 0 && in_act <= 2, E2EP_EINVAL,
-               "e2ep_dwconv_bwd: in_scale / in_shift both or neither, in_act 0..2");
-  E2EP_REQUIRE(gy && x && w && dx && dw, E2EP_EINVAL, "e2ep_dwconv_bwd: null tensor");
+  const char *fn = "e2ep_dwconv_bwd";
+  const DwPlan p = dw_plan(dw_geom(dims));
   const DwIn tf{in_scale, in_shift, in_act};
+  if (int e = dw_check(fn, p, io, p.dgrad_io, tf, true, workspace, workspace_bytes)) return e;
+  E2EP_REQUIRE(p.pair != DW_PAIR_NONE, E2EP_EINVAL,
+               "%s: no paired backward for this geometry (e2ep_dwconv_bwd_pair_ok returned 0)", fn);
+  E2EP_REQUIRE(gy && x && w && dx && dw, E2EP_EINVAL, "%s: null tensor", fn);
   hipStream_t s = as_stream(stream);
-  if (s2) {
-    const DwStrip d = dw_strip(g.K, 2, g.W, g.P, g.Q);
-    const int vw = cdiv(d.IR * (g.W / 4), 64) <= 2 ? 2 : DW_MAXV;
-    const int sp = dw_wgrad_splits(g);
-    DwPart part{static_cast<float *>(workspace), dw,
-                (sp > 1 && g_tune[TUNE_SPLITK_FOLD] == 2) ? handoff_slots(g.C, s) : nullptr};
-    const size_t shm = 4 * (size_t)std::max(p2.GR * p2.WPg, d.IR * d.WP) * 4;
-    const dim3 grid(g.C * sp + cdiv(p2.units, 4));
-#define DWP2B(KV, PLPV, OFFV, VWV, BV)                                                             \
-  hipLaunchKernelGGL((k_dw_bwd_pair_s2<KV, PLPV, OFFV, VWV, BV>), grid, dim3(256), shm, s,         \
-                     static_cast<const dw_to<BV> *>(gy), w, p2.RO, p2.GR, p2.WPg, p2.upp, p2.units, \
-                     static_cast<dw_to<BV> *>(dx), x, g, d, sp, part, tf)
-#define DWP2(KV, PLPV, OFFV)                                                                       \
-  do {                                                                                             \
-    if (vw == 2 && hb) DWP2B(KV, PLPV, OFFV, 2, true);                                             \
-    else if (vw == 2) DWP2B(KV, PLPV, OFFV, 2, false);                                             \
-    else if (hb) DWP2B(KV, PLPV, OFFV, DW_MAXV, true);                                             \
-    else DWP2B(KV, PLPV, OFFV, DW_MAXV, false);                                                    \
-  } while (0)
-    // PLP = pad_left & 1, OFF = -pad_left mod 4 (dw_off)
-    if (g.K == 3 && g.pl == 0) DWP2(3, 0, 0);
-    else if (g.K == 3) DWP2(3, 1, 3);
-    else if (g.pl == 1) DWP2(5, 1, 3);
-    else DWP2(5, 0, 2);
-#undef DWP2
-#undef DWP2B
-    if (sp > 1 && !part.cnt)
-      hipLaunchKernelGGL(k_dw_wgrad_finalize, dim3(cdiv(g.C * g.K * g.K, 256)), dim3(256), 0, s,
-                         part.part, g.C, g.K * g.K, sp, dw);
-    return launch_status("e2ep_dwconv_bwd");
-  }
-  const DwStrip dt = dw_strip(t.K, 1, t.W, t.P, t.Q);
-  const int units = t.N * t.C * dt.units_per_plane;
-  const int nd = dw_fwd_blocks(units);
-  const int vd = cdiv(dt.IR * (t.W / 4), 64) <= 2 ? 2 : DW_MAXV;
-  const DwStrip d = dw_strip(g.K, 1, g.W, g.P, g.Q);
-  const int vw = cdiv(d.IR * (g.W / 4), 64) <= 2 ? 2 : DW_MAXV;
-  const int sp = dw_wgrad_splits(g);
-  DwPart part{static_cast<float *>(workspace), dw,
-              (sp > 1 && g_tune[TUNE_SPLITK_FOLD] == 2) ? handoff_slots(g.C, s) : nullptr};
-  const size_t shm = 4 * (size_t)std::max(dt.IR * dt.WP, d.IR * d.WP) * 4;
-  const dim3 grid(nd + g.C * sp);
-#define DWPB(KV, OFFV, VDV, VWV, BV)                                                              \
-  hipLaunchKernelGGL((k_dw_bwd_pair<KV, OFFV, VDV, VWV, BV>), grid, dim3(256), shm, s,             \
-                     static_cast<const dw_to<BV> *>(gy), w, t, dt, units, static_cast<dw_to<BV> *>(dx), \
-                     nd, x, g, d, sp, part, tf)
-#define DWP(KV, OFFV, VDV, VWV)                          \
-  do {                                                   \
-    if (hb) DWPB(KV, OFFV, VDV, VWV, true);              \
-    else DWPB(KV, OFFV, VDV, VWV, false);                \
-  } while (0)
-#define DWP_V(KV, OFFV)                                  \
-  do {                                                   \
-    if (vd == 2 && vw == 2) DWP(KV, OFFV, 2, 2);         \
-    else if (vd == 2) DWP(KV, OFFV, 2, DW_MAXV);         \
-    else if (vw == 2) DWP(KV, OFFV, DW_MAXV, 2);         \
-    else DWP(KV, OFFV, DW_MAXV, DW_MAXV);                \
-  } while (0)
-  if (g.K == 3) DWP_V(3, 3);
-  else DWP_V(5, 2);
-#undef DWP_V
-#undef DWP
-#undef DWPB
-  if (sp > 1 && !part.cnt)
-    hipLaunchKernelGGL(k_dw_wgrad_finalize, dim3(cdiv(g.C * g.K * g.K, 256)), dim3(256), 0, s,
-                       part.part, g.C, g.K * g.K, sp, dw);
-  return launch_status("e2ep_dwconv_bwd");
+  const DwPart part = dw_part(p, workspace, dw, s);
+  if (p.pair == DW_PAIR_S1) dw_launch_pair_s1(p, io != 0, gy, x, w, dx, part, tf, s);
+  else dw_launch_pair_s2(p, io != 0, gy, x, w, dx, part, tf, s);
+  dw_finalize(p, part, s);
+  return launch_status(fn);
 }
 
 }  // extern "C"
+

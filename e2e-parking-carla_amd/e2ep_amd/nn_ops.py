@@ -429,6 +429,37 @@ def _dw_pairable(d):
     return _DW_PAIR[0] and _lib.load().e2ep_dwconv_bwd_pair_ok(d) == 1
 
 
+def _dw_backward(gy, x, w, d, scale, shift, act, want_x, want_w, hb, label):
+    """The depthwise conv's backward for _DwConv and _BnActDwConv (scale / shift / act: the
+    input transform of the fused form): (dx, dw, fork), each None when not wanted.  Both
+    gradients in one launch where _dw_pairable; otherwise the weight gradient on the side stream
+    (conv._Fork), which the caller joins once its own launches are issued.  hb: gy is stored
+    bf16, and so is dx."""
+    s = _lib.stream()
+    dx = dw = fork = None
+    if want_w:
+        dw = torch.empty_like(w)
+        ws = _ws(_lib.load().e2ep_dwconv_wgrad_workspace(d), x.device)
+    if want_x:
+        dx = torch.empty(x.shape, dtype=torch.bfloat16 if hb else torch.float32, device=x.device)
+    if want_x and want_w and _dw_pairable(d):
+        with timing.region(timing.name("dwconv_bwd", gy.shape, label)):
+            _lib.call("e2ep_dwconv_bwd", _lib.ptr(gy), _lib.ptr(x), _lib.ptr(w), d, _lib.ptr(scale),
+                      _lib.ptr(shift), act, _lib.ptr(dx), _lib.ptr(ws), _lib.nbytes(ws), _lib.ptr(dw), s,
+                      _lib.io_mask(dy=hb, dx=hb))
+        return dx, dw, None
+    if want_w:
+        fork = conv._Fork(x.device, on=want_x, work_us=conv.est_us(nbytes=4.0 * (x.numel() + gy.numel())))
+        with fork, timing.region(timing.name("dwconv_wgrad", gy.shape, label)):
+            _lib.call("e2ep_dwconv_wgrad", _lib.ptr(gy), _lib.ptr(x), d, _lib.ptr(scale), _lib.ptr(shift),
+                      act, _lib.ptr(ws), _lib.nbytes(ws), _lib.ptr(dw), _lib.stream(), _lib.io_mask(dy=hb))
+    if want_x:
+        with timing.region(timing.name("dwconv_dgrad", gy.shape, label)):
+            _lib.call("e2ep_dwconv_dgrad", _lib.ptr(gy), _lib.ptr(w), d, _lib.ptr(dx), s,
+                      _lib.io_mask(dy=hb, dx=hb))
+    return dx, dw, fork
+
+
 # ------------------------------------------------------------------------------------------
 class _DwConv(torch.autograd.Function):
     @staticmethod
@@ -449,29 +480,8 @@ class _DwConv(torch.autograd.Function):
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
         gy = gy.contiguous()
-        d = _lib.dims(ctx.dims)
-        s = _lib.stream()
-        dx = dw = None
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _dw_pairable(d):
-            dx, dw = torch.empty_like(x), torch.empty_like(w)
-            ws = _ws(_lib.load().e2ep_dwconv_wgrad_workspace(d), x.device)
-            with timing.region(timing.name("dwconv_bwd", gy.shape, "_DwConv")):
-                _lib.call("e2ep_dwconv_bwd", _lib.ptr(gy), _lib.ptr(x), _lib.ptr(w), d, None, None, 0,
-                          _lib.ptr(dx), _lib.ptr(ws), _lib.nbytes(ws), _lib.ptr(dw), s, 0)
-            return dx, dw, None, None
-        fork = None
-        if ctx.needs_input_grad[1]:  # weight gradient on the side stream (conv._Fork)
-            dw = torch.empty_like(w)
-            ws = _ws(_lib.load().e2ep_dwconv_wgrad_workspace(d), x.device)
-            fork = conv._Fork(x.device, on=ctx.needs_input_grad[0],
-                              work_us=conv.est_us(nbytes=4.0 * (x.numel() + gy.numel())))
-            with fork, timing.region(timing.name("dwconv_wgrad", gy.shape, "_DwConv")):
-                _lib.call("e2ep_dwconv_wgrad", _lib.ptr(gy), _lib.ptr(x), d, None, None, 0,
-                          _lib.ptr(ws), _lib.nbytes(ws), _lib.ptr(dw), _lib.stream(), 0)
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            with timing.region(timing.name("dwconv_dgrad", gy.shape, "_DwConv")):
-                _lib.call("e2ep_dwconv_dgrad", _lib.ptr(gy), _lib.ptr(w), d, _lib.ptr(dx), s, 0)
+        dx, dw, fork = _dw_backward(gy, x, w, _lib.dims(ctx.dims), None, None, 0,
+                                    ctx.needs_input_grad[0], ctx.needs_input_grad[1], False, "_DwConv")
         if fork is not None:
             fork.join()
         return dx, dw, None, None
@@ -516,38 +526,15 @@ class _BnActDwConv(torch.autograd.Function):
         d = _lib.dims(ctx.dims)
         s = _lib.stream()
         nig = ctx.needs_input_grad
-        dw = dx = dg = db = None
-        fork = None
+        dx = dg = db = None
         want_t = nig[0] or nig[1] or nig[2]
-        paired = nig[9] and want_t and _dw_pairable(d)
         # bf16 storage: the incoming gradient (at the stored bf16 output) is bf16, and so is the
         # data gradient handed to the BN backward
         hb = _is_bf16(gy)
-        tdt = torch.bfloat16 if hb else torch.float32
-        if paired:  # both gradients in one launch
-            dw = torch.empty_like(w)
-            dt = torch.empty(x.shape, dtype=tdt, device=x.device)  # gradient at the activation output
-            wsw = _ws(_lib.load().e2ep_dwconv_wgrad_workspace(d), x.device)
-            with timing.region(timing.name("dwconv_bwd", gy.shape, "_BnActDwConv")):
-                _lib.call("e2ep_dwconv_bwd", _lib.ptr(gy), _lib.ptr(x), _lib.ptr(w), d,
-                          _lib.ptr(stats[2]), _lib.ptr(stats[3]), ctx.act, _lib.ptr(dt),
-                          _lib.ptr(wsw), _lib.nbytes(wsw), _lib.ptr(dw), s,
-                          _lib.io_mask(dy=hb, dx=hb))
-        elif nig[9]:  # weight gradient on the side stream (conv._Fork)
-            dw = torch.empty_like(w)
-            wsw = _ws(_lib.load().e2ep_dwconv_wgrad_workspace(d), x.device)
-            fork = conv._Fork(x.device, on=want_t,
-                              work_us=conv.est_us(nbytes=4.0 * (x.numel() + gy.numel())))
-            with fork, timing.region(timing.name("dwconv_wgrad", gy.shape, "_BnActDwConv")):
-                _lib.call("e2ep_dwconv_wgrad", _lib.ptr(gy), _lib.ptr(x), d, _lib.ptr(stats[2]),
-                          _lib.ptr(stats[3]), ctx.act, _lib.ptr(wsw), _lib.nbytes(wsw), _lib.ptr(dw), _lib.stream(),
-                          _lib.io_mask(dy=hb))
+        # dt: the gradient at the activation output
+        dt, dw, fork = _dw_backward(gy, x, w, d, stats[2], stats[3], ctx.act, want_t, nig[9], hb,
+                                    "_BnActDwConv")
         if want_t:
-            if not paired:
-                dt = torch.empty(x.shape, dtype=tdt, device=x.device)  # gradient at the activation output
-                with timing.region(timing.name("dwconv_dgrad", gy.shape, "_BnActDwConv")):
-                    _lib.call("e2ep_dwconv_dgrad", _lib.ptr(gy), _lib.ptr(w), d, _lib.ptr(dt), s,
-                              _lib.io_mask(dy=hb, dx=hb))
             dx, dg, db = _like(x, nig[0]), _like(gamma, nig[1]), _like(beta, nig[2])
             ws = _ws(_lib.load().e2ep_bn_workspace(N, C, H, W), x.device)
             with timing.region(timing.name("bn_bwd", x.shape, "_BnActDwConv")):

@@ -190,7 +190,11 @@ def test_resize_fwd_vector_path_bitwise(shape, out):
                                   (2, 40, 32, 32, 5, 1, (2, 2, 2, 2)), (3, 16, 16, 16, 3, 1, (1, 1, 1, 1)),
                                   (2, 12, 24, 20, 5, 1, (2, 2, 2, 2)), (2, 16, 32, 32, 5, 2, (1, 2, 1, 2)),
                                   (2, 8, 20, 24, 3, 2, (0, 1, 0, 1)), (2, 6, 64, 48, 5, 2, (2, 2, 2, 2)),
-                                  (2, 16, 32, 32, 5, 1, (3, 1, 3, 1))])
+                                  (2, 16, 32, 32, 5, 1, (3, 1, 3, 1)),
+                                  # outside the strip kernels' halo bound (5 columns of left / of
+                                  # right pad): the forward and the weight gradient run the
+                                  # generic kernels (tests/test_dwconv_plan_cpu.py)
+                                  (2, 8, 16, 16, 3, 1, (5, 1, 1, 1)), (2, 8, 16, 16, 3, 1, (1, 5, 1, 1))])
 @pytest.mark.parametrize("variant", [(2, 0), (1, 3)])
 def test_depthwise(case, variant):
     """variant = (e2ep_tune key 23, key 24): the strip kernels' LDS window reads (2 = 16-B
