@@ -12,6 +12,7 @@
 // Backward recomputes the pre-activation from x (no saved activation tensor).
 #include <algorithm>
 
+#include "bns_layout.h"
 #include "common.h"
 
 // Contraction only within one expression (a*b + c -> fma): the fp32 and bf16-storage
@@ -582,15 +583,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(
 // apply).  Same fp64 statistics and element arithmetic as the split kernels above; the
 // summation is in a fixed order (thread t takes vectors t, t + 1024, ...), so deterministic.
 // ------------------------------------------------------------------------------------------
-constexpr int BNS_T = 256, BNS_R = 8;
-static int g_bn_small = 1;  // e2ep_bn_small(0) routes every shape to the split kernels (tests, A/B)
-// largest channel (in float4 vectors) the single-launch kernels take, forward / backward
-// (e2ep_bn_small_limits, A/B timing; at most BNS_R * BNS_T).  In the replayed C2 step, blocks
-// of 1024 threads for channels up to 32768 elements measured 0.25 ms/step slower than the
-// split kernels there (25.45 vs 25.19 ms, profiles/r02/session6/wgrad_target_bn_limits_ab.txt),
-// so only the 256-thread shapes take the single launch.
-static int g_bns_fwd_max = BNS_R * BNS_T, g_bns_bwd_max = BNS_R * BNS_T;
-static bool bn_small_enabled() { return g_bn_small != 0; }
+// (BNS_T, BNS_R and the <threads, vectors per thread> layouts: bns_layout.h)
 
 template <int T>
 __device__ __forceinline__ void block_sum2_t(double &s, double &q) {
@@ -751,38 +744,6 @@ __global__ void __launch_bounds__(T) k_bn_bwd_small(
   }
 }
 
-// vectors per thread of the single-launch kernels (R = 0: the channel is too large); 256-thread
-// blocks, every block of a step resident at once
-static int bns_r(int totv, int &threads) {
-  threads = BNS_T;
-  const int per = cdiv(totv, threads);
-  if (per <= 1) return 1;
-  if (per <= 2) return 2;
-  if (per <= 4) return 4;
-  if (per <= BNS_R) return 8;
-  return 0;
-}
-#define BNS_LAUNCH(KERNEL, R, TH, ...) BNS_LAUNCH_T(KERNEL, , R, TH, __VA_ARGS__)
-// TYPES: the kernel's storage-type template arguments after <threads, R> (", bf16_t, float, ..."
-// or empty)
-#define BNS_LAUNCH_T(KERNEL, TYPES, R, TH, ...)                                                   \
-  do {                                                                                            \
-    (void)(TH);                                                                                   \
-    if (R == 1) hipLaunchKernelGGL((KERNEL<BNS_T, 1 TYPES>), dim3(C), dim3(BNS_T), 0, s, __VA_ARGS__);  \
-    else if (R == 2 && g_tune[TUNE_BNS_WIDE_LO] == 2)                                             \
-      hipLaunchKernelGGL((KERNEL<2 * BNS_T, 1 TYPES>), dim3(C), dim3(2 * BNS_T), 0, s, __VA_ARGS__); \
-    else if (R == 2) hipLaunchKernelGGL((KERNEL<BNS_T, 2 TYPES>), dim3(C), dim3(BNS_T), 0, s, __VA_ARGS__); \
-    else if (R == 4 && g_tune[TUNE_BNS_WIDE_LO] == 2)                                             \
-      hipLaunchKernelGGL((KERNEL<2 * BNS_T, 2 TYPES>), dim3(C), dim3(2 * BNS_T), 0, s, __VA_ARGS__); \
-    else if (R == 4) hipLaunchKernelGGL((KERNEL<BNS_T, 4 TYPES>), dim3(C), dim3(BNS_T), 0, s, __VA_ARGS__); \
-    else if (g_tune[TUNE_BNS_WIDE] == 2)                                                         \
-      hipLaunchKernelGGL((KERNEL<2 * BNS_T, 4 TYPES>), dim3(C), dim3(2 * BNS_T), 0, s, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<BNS_T, 8 TYPES>), dim3(C), dim3(BNS_T), 0, s, __VA_ARGS__);   \
-  } while (0)
-// (e2ep_tune key 25 = 2: channels that need 8 float4 per thread at 256 threads run 512-thread
-// blocks of 4 per thread instead: half the registers per thread, twice the waves per channel;
-// key 26 = 2 does the same for the 2- and 4-vector cases)
-
 // elementwise activation forward/backward (for activations not fused into a BN)
 __global__ void k_act_fwd(const float *__restrict__ x, long long n, int act, float *__restrict__ y) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -794,213 +755,91 @@ __global__ void k_act_bwd(const float *__restrict__ x, const float *__restrict__
   if (i < n) dx[i] = dy[i] * act_bwd(x[i], act);
 }
 
-static int bn_splits(long long per_channel, int C) {
-  // enough workgroups to fill the chip (e2ep_tune key 0) with >= key-1 elements each
-  long long want = (g_tune[TUNE_BN_SPLIT_TARGET] + C - 1) / C;
-  long long cap = per_channel / g_tune[TUNE_BN_SPLIT_MIN];
-  long long s = want < cap ? want : cap;
-  if (s < 1) s = 1;
-  if (s > 256) s = 256;
-  return (int)s;
+// ------------------------------------------------------------------------------------------
+// Host half.  bn_plan() is the only place that says which kernels run for a shape, on which
+// layout and grid; the queries and the launch entry points read what it returns.
+// ------------------------------------------------------------------------------------------
+static int g_bn_small = 1;  // e2ep_bn_small(0) routes every shape to the split kernels (tests, A/B)
+// largest channel (in float4 vectors) the single-launch kernels take, forward / backward
+// (e2ep_bn_small_limits, A/B timing; at most BNS_R * BNS_T).  In the replayed C2 step, blocks
+// of 1024 threads for channels up to 32768 elements measured 0.25 ms/step slower than the
+// split kernels there (25.45 vs 25.19 ms, profiles/r02/session6/wgrad_target_bn_limits_ab.txt),
+// so only the 256-thread shapes take the single launch.
+static int g_bns_fwd_max = BNS_R * BNS_T, g_bns_bwd_max = BNS_R * BNS_T;
+
+struct BnGeom {
+  bool valid;       // N, C, H, W > 0; nothing below is set otherwise
+  int N, C, HW;
+  bool v4;          // float4 accesses: H * W % 4 == 0 (and `aligned`)
+  int HWv, totv;    // vectors (v4) or elements of a plane / of a channel
+  long long per_c;  // elements of a channel
+};
+// aligned: e2ep_bn_apply alone folds the 16-byte alignment of x, y and res into v4; every other
+// entry point takes H * W % 4 == 0 as enough
+static BnGeom bn_geom(int N, int C, int H, int W, bool aligned = true) {
+  BnGeom g{};
+  g.valid = N > 0 && C > 0 && H > 0 && W > 0;
+  if (!g.valid) return g;
+  g.N = N, g.C = C, g.HW = H * W;
+  g.per_c = (long long)N * H * W;
+  g.v4 = (g.HW & 3) == 0 && aligned;
+  g.HWv = g.v4 ? g.HW / 4 : g.HW;
+  g.totv = (int)((long long)N * g.HWv);
+  return g;
 }
 
-// vectors per apply workgroup (4 per thread)
-#define APPLY_PER (g_tune[TUNE_BN_APPLY_PER])
+struct BnPlan {
+  BnGeom g;
+  // Single launch (k_bn_fwd_small / k_bn_bwd_small) and its layout; {0, 0}: the split route.
+  // e2ep_bn_fwd / e2ep_bn_stats take `fwd` only when train: eval goes straight to apply /
+  // finalize with part = nullptr, sp = 1.  e2ep_bn_bwd_planes never takes `bwd`.
+  BnsLayout fwd, bwd;
+  // Split route.  The workspace is sized from the requested `splits`, not from the smaller
+  // effective sp.  Forward and statistics demand it whenever train, even where `fwd` is
+  // taken; the backward only where `bwd` is not.
+  int splits;        // e2ep_tune key 0 workgroups over the C channels, each of >= key-1 elements; 1 .. 256
+  size_t workspace;  // C x splits x 2 doubles
+  bool launch_ok;    // what a launch needs besides g.valid: C <= 65535, N * H * W < 2^31; the
+                     // fields below are set only then (and fwd / bwd are {0, 0} otherwise)
+  int sp, per;       // slices per channel of `per` vectors: grid (C, sp) of k_bn_stats / k_bn_bwd_reduce
+  int apply_per, apply_blocks;  // vectors per apply workgroup (4 per thread; e2ep_tune key 2): grid (C, apply_blocks)
+  // sweep direction of the split passes (e2ep_tune key 33 = 1 + mask): mask bit 0 backward
+  // apply back to front, bit 1 backward reduction back to front, bit 2 forward apply back to front
+  int rev_apply, rev_reduce, rev_fwd;
+};
 
-// sweep direction of the split BN passes (e2ep_tune key 33 = 1 + mask): mask bit 0 backward
-// apply back to front, bit 1 backward reduction back to front, bit 2 forward apply back to front
-static int bn_rev_apply() { return ((g_tune[TUNE_BN_ORDER] - 1) >> 0) & 1; }
-static int bn_rev_reduce() { return ((g_tune[TUNE_BN_ORDER] - 1) >> 1) & 1; }
-static int bn_rev_fwd() { return ((g_tune[TUNE_BN_ORDER] - 1) >> 2) & 1; }
-
-}  // namespace e2ep
-
-using namespace e2ep;
-
-extern "C" {
-
-size_t e2ep_bn_workspace(int N, int C, int H, int W) {
-  const int sp = bn_splits((long long)N * H * W, C);
-  return (size_t)C * sp * 2 * sizeof(double);
-}
-
-int e2ep_bn_fwd(const float *x, const float *gamma, const float *beta, const float *res,
-                const float *dc_rand, float dc_keep, float *running_mean, float *running_var,
-                int N, int C, int H, int W, int train, float momentum, float eps, int act,
-                float *mean, float *invstd, float *y, void *workspace, size_t workspace_bytes,
-                void *stream) {
-  E2EP_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && (long long)N * H * W < (1LL << 31),
-               E2EP_EINVAL, "e2ep_bn_fwd: bad shape");
-  E2EP_REQUIRE(!train || (workspace && workspace_bytes >= e2ep_bn_workspace(N, C, H, W)),
-               E2EP_EINVAL, "%s: workspace %zu bytes < %zu (e2ep_bn_workspace)", "e2ep_bn_fwd",
-               workspace_bytes, e2ep_bn_workspace(N, C, H, W));
-
-  E2EP_REQUIRE(act >= 0 && act <= 2, E2EP_EINVAL, "e2ep_bn_fwd: act must be 0/1/2");
-  E2EP_REQUIRE(train || (running_mean && running_var), E2EP_EINVAL,
-               "e2ep_bn_fwd: eval needs running stats");
-  E2EP_REQUIRE(!dc_rand || dc_keep > 0.f, E2EP_EINVAL, "e2ep_bn_fwd: drop-connect keep must be > 0");
-  hipStream_t s = as_stream(stream);
-  const int HW = H * W;
-  const long long per_c = (long long)N * HW;
-  const bool v4 = (HW & 3) == 0;
-  const int HWv = v4 ? HW / 4 : HW;
-  const int totv = N * HWv;
-  const bool small_ok = bn_small_enabled();
-  int th = 0;
-  const int R = (train && v4 && small_ok && totv <= g_bns_fwd_max) ? bns_r(totv, th) : 0;
-  if (R) {
-    BNS_LAUNCH(k_bn_fwd_small, R, th, x, per_c, eps, momentum, running_mean, running_var, mean, invstd,
-               gamma, beta, res, dc_rand, dc_keep, N, C, HWv, act, y, nullptr, nullptr);
-    return launch_status("e2ep_bn_fwd");
+static BnPlan bn_plan(const BnGeom &g) {
+  BnPlan p{};
+  p.g = g;
+  if (!g.valid) return p;
+  const long long want = (g_tune[TUNE_BN_SPLIT_TARGET] + g.C - 1) / g.C;
+  const long long cap = g.per_c / g_tune[TUNE_BN_SPLIT_MIN];
+  p.splits = (int)std::max(1LL, std::min({want, cap, 256LL}));
+  p.workspace = (size_t)g.C * p.splits * 2 * sizeof(double);
+  p.launch_ok = g.C <= 65535 && g.per_c < (1LL << 31);
+  if (!p.launch_ok) return p;
+  if (g.v4 && g_bn_small != 0) {
+    if (g.totv <= g_bns_fwd_max) p.fwd = bns_layout(g.totv);
+    if (g.totv <= g_bns_bwd_max) p.bwd = bns_layout(g.totv);
   }
-  double *part = nullptr;
-  int sp = 1;
-  if (train) {
-    sp = bn_splits(per_c, C);
-    const int per = cdiv(totv, sp);
-    sp = cdiv(totv, per);
-    part = static_cast<double *>(workspace);
-    if (v4)
-      hipLaunchKernelGGL(k_bn_stats<4>, dim3(C, sp), dim3(256), 0, s, x, N, C, HWv, sp, per, part);
-    else
-      hipLaunchKernelGGL(k_bn_stats<1>, dim3(C, sp), dim3(256), 0, s, x, N, C, HWv, sp, per, part);
-  }
-  const dim3 grid(C, cdiv(totv, APPLY_PER));
-  if (v4)
-    hipLaunchKernelGGL(k_bn_apply<4>, grid, dim3(256), 0, s, x, part, sp, per_c, eps, momentum,
-                       running_mean, running_var, mean, invstd, gamma, beta, res, dc_rand, dc_keep,
-                       N, C, HWv, APPLY_PER, act, y, nullptr, nullptr, bn_rev_fwd());
-  else
-    hipLaunchKernelGGL(k_bn_apply<1>, grid, dim3(256), 0, s, x, part, sp, per_c, eps, momentum,
-                       running_mean, running_var, mean, invstd, gamma, beta, res, dc_rand, dc_keep,
-                       N, C, HWv, APPLY_PER, act, y, nullptr, nullptr, bn_rev_fwd());
-  return launch_status("e2ep_bn_fwd");
+  p.per = cdiv(g.totv, p.splits);
+  p.sp = cdiv(g.totv, p.per);
+  p.apply_per = g_tune[TUNE_BN_APPLY_PER];
+  p.apply_blocks = cdiv(g.totv, p.apply_per);
+  const int order = g_tune[TUNE_BN_ORDER] - 1;
+  p.rev_apply = order & 1, p.rev_reduce = (order >> 1) & 1, p.rev_fwd = (order >> 2) & 1;
+  return p;
 }
 
-}  // extern "C"
-
-template <typename TX>
-static int bn_stats_impl(const TX *x, const float *gamma, const float *beta, float *running_mean,
-                         float *running_var, int N, int C, int H, int W, int train, float momentum,
-                         float eps, float *mean, float *invstd, float *scale, float *shift,
-                         void *workspace, size_t workspace_bytes, void *stream) {
-  E2EP_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && (long long)N * H * W < (1LL << 31),
-               E2EP_EINVAL, "e2ep_bn_stats: bad shape");
-  E2EP_REQUIRE(!train || (workspace && workspace_bytes >= e2ep_bn_workspace(N, C, H, W)),
-               E2EP_EINVAL, "%s: workspace %zu bytes < %zu (e2ep_bn_workspace)", "e2ep_bn_stats",
-               workspace_bytes, e2ep_bn_workspace(N, C, H, W));
-
-  E2EP_REQUIRE(train || (running_mean && running_var), E2EP_EINVAL,
-               "e2ep_bn_stats: eval needs running stats");
-  E2EP_REQUIRE(mean && invstd && scale && shift, E2EP_EINVAL, "e2ep_bn_stats: null output");
-  hipStream_t s = as_stream(stream);
-  const int HW = H * W;
-  const long long per_c = (long long)N * HW;
-  const bool v4 = (HW & 3) == 0;
-  const int HWv = v4 ? HW / 4 : HW;
-  const int totv = N * HWv;
-  const bool small_ok = bn_small_enabled();
-  int th = 0;
-  const int R = (train && v4 && small_ok && totv <= g_bns_fwd_max) ? bns_r(totv, th) : 0;
-  if (R) {
-#define E2EP_BN_TYPES , TX
-    BNS_LAUNCH_T(k_bn_fwd_small, E2EP_BN_TYPES, R, th, x, per_c, eps, momentum, running_mean, running_var,
-                 mean, invstd, gamma, beta, nullptr, nullptr, 1.f, N, C, HWv, 0, nullptr, scale, shift);
-#undef E2EP_BN_TYPES
-    return launch_status("e2ep_bn_stats");
-  }
-  double *part = nullptr;
-  int sp = 1;
-  if (train) {
-    sp = bn_splits(per_c, C);
-    const int per = cdiv(totv, sp);
-    sp = cdiv(totv, per);
-    part = static_cast<double *>(workspace);
-    if (v4)
-      hipLaunchKernelGGL((k_bn_stats<4, TX>), dim3(C, sp), dim3(256), 0, s, x, N, C, HWv, sp, per, part);
-    else
-      hipLaunchKernelGGL((k_bn_stats<1, TX>), dim3(C, sp), dim3(256), 0, s, x, N, C, HWv, sp, per, part);
-  }
-  hipLaunchKernelGGL(k_bn_finalize, dim3(C), dim3(256), 0, s, part, sp, per_c, eps, momentum,
-                     running_mean, running_var, mean, invstd, gamma, beta, scale, shift);
-  return launch_status("e2ep_bn_stats");
+// What every launch entry point requires of its shape and, where need_ws, of its workspace
+// (0, or the status to hand back)
+static int bn_check(const char *fn, const BnPlan &p, bool need_ws = false,
+                    const void *workspace = nullptr, size_t workspace_bytes = 0) {
+  E2EP_REQUIRE(p.launch_ok, E2EP_EINVAL, "%s: bad shape", fn);
+  E2EP_REQUIRE(!need_ws || (workspace && workspace_bytes >= p.workspace), E2EP_EINVAL,
+               "%s: workspace %zu bytes < %zu (e2ep_bn_workspace)", fn, workspace_bytes, p.workspace);
+  return 0;
 }
-
-extern "C" {
-
-int e2ep_bn_stats(const void *x, const float *gamma, const float *beta, float *running_mean,
-                  float *running_var, int N, int C, int H, int W, int train, float momentum,
-                  float eps, float *mean, float *invstd, float *scale, float *shift,
-                  void *workspace, size_t workspace_bytes, void *stream, int io) {
-  E2EP_REQUIRE(io == 0 || (io == E2EP_IO_X_BF16 && (H * W) % 4 == 0), E2EP_EINVAL,
-               "e2ep_bn_stats: storage mask %d not supported (0 or X bf16, H*W %% 4 == 0)", io);
-  if (io)
-    return bn_stats_impl(static_cast<const bf16_t *>(x), gamma, beta, running_mean, running_var, N, C,
-                         H, W, train, momentum, eps, mean, invstd, scale, shift, workspace,
-                         workspace_bytes, stream);
-  return bn_stats_impl(static_cast<const float *>(x), gamma, beta, running_mean, running_var, N, C, H,
-                       W, train, momentum, eps, mean, invstd, scale, shift, workspace, workspace_bytes,
-                       stream);
-}
-
-int e2ep_bn_fwd_split(int N, int C, int H, int W) {
-  if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-  const int HW = H * W;
-  const bool v4 = (HW & 3) == 0;
-  const int totv = N * (v4 ? HW / 4 : HW);
-  int th = 0;
-  return (v4 && bn_small_enabled() && totv <= g_bns_fwd_max && bns_r(totv, th)) ? 0 : 1;
-}
-
-size_t e2ep_bn_finalize_part_workspace(int C, int tiles) {
-  (void)C;
-  (void)tiles;
-  return 0;  // one launch, no workspace (kept in the ABI for a future split plan)
-}
-
-int e2ep_bn_finalize_part(const double *part, int tiles, const float *gamma, const float *beta,
-                          float *running_mean, float *running_var, int N, int C, int H, int W,
-                          float momentum, float eps, float *mean, float *invstd, float *scale,
-                          float *shift, void *workspace, size_t workspace_bytes, void *stream) {
-  E2EP_REQUIRE(part && tiles > 0 && N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535, E2EP_EINVAL,
-               "e2ep_bn_finalize_part: bad arguments");
-  E2EP_REQUIRE(mean && invstd && scale && shift, E2EP_EINVAL, "e2ep_bn_finalize_part: null output");
-  E2EP_REQUIRE(!running_mean == !running_var, E2EP_EINVAL,
-               "e2ep_bn_finalize_part: running_mean / running_var both or neither");
-  (void)workspace;
-  (void)workspace_bytes;
-  hipLaunchKernelGGL(k_bn_finalize_tiles, dim3(cdiv(C, FT_CH)), dim3(FT_CH * FT_GROUPS), 0, as_stream(stream),
-                     part, tiles, C, (long long)N * H * W, eps, momentum, running_mean, running_var,
-                     mean, invstd, gamma, beta, scale, shift);
-  return launch_status("e2ep_bn_finalize_part");
-}
-
-int e2ep_bn_apply(const float *x, const float *scale, const float *shift, const float *res,
-                  const float *dc_rand, float dc_keep, int N, int C, int H, int W, int act,
-                  float *y, void *stream) {
-  E2EP_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && (long long)N * H * W < (1LL << 31),
-               E2EP_EINVAL, "e2ep_bn_apply: bad shape");
-  E2EP_REQUIRE(x && y && scale && shift && act >= 0 && act <= 2, E2EP_EINVAL,
-               "e2ep_bn_apply: bad arguments");
-  E2EP_REQUIRE(!dc_rand || dc_keep > 0.f, E2EP_EINVAL, "e2ep_bn_apply: drop-connect keep must be > 0");
-  const int HW = H * W;
-  const bool v4 = (HW & 3) == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0;
-  const int HWv = v4 ? HW / 4 : HW;
-  const int totv = N * HWv;
-  const dim3 grid(C, cdiv(totv, APPLY_PER));
-  hipStream_t s = as_stream(stream);
-  if (v4)
-    hipLaunchKernelGGL(k_bn_apply<4>, grid, dim3(256), 0, s, x, nullptr, 1, (long long)N * HW, 0.f,
-                       0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, res, dc_rand,
-                       dc_keep, N, C, HWv, APPLY_PER, act, y, scale, shift, bn_rev_fwd());
-  else
-    hipLaunchKernelGGL(k_bn_apply<1>, grid, dim3(256), 0, s, x, nullptr, 1, (long long)N * HW, 0.f,
-                       0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, res, dc_rand,
-                       dc_keep, N, C, HWv, APPLY_PER, act, y, scale, shift, bn_rev_fwd());
-  return launch_status("e2ep_bn_apply");
-}
-
-}  // extern "C"
 
 // storage types of (x, dy, dx) for an io mask (e2ep.h E2EP_IO_*): fp32, or the bf16
 // combinations the step stores — the depthwise output's BN (_bn1: x and dx bf16, dy bf16 too
@@ -1016,145 +855,293 @@ static bool bn_io_ok(int io) {
   return io == BNIO_F32 || io == BNIO_XDX || io == BNIO_ALL || io == BNIO_DY;
 }
 
-template <typename TX, typename TD, typename TO>
-static int bn_bwd_impl(const TX *x, const TD *dy, const float *mean, const float *invstd,
-                       const float *gamma, const float *beta, const float *res,
-                       const float *dc_rand, float dc_keep, const BnGate &gt, int N, int C, int H,
-                       int W, int train, int act, TO *dx, float *dgamma, float *dbeta, float *dres,
-                       void *workspace, size_t workspace_bytes, hipStream_t s) {
-  const int HW = H * W;
-  const long long per_c = (long long)N * HW;
-  const bool v4 = (HW & 3) == 0;
-  const int HWv = v4 ? HW / 4 : HW;
-  const int totv = N * HWv;
-  const bool small_ok = bn_small_enabled();
-  int th = 0;
-  const int R = (v4 && small_ok && totv <= g_bns_bwd_max) ? bns_r(totv, th) : 0;
-  if (R) {
-#define E2EP_BN_TYPES , TX, TD, TO
-    BNS_LAUNCH_T(k_bn_bwd_small, E2EP_BN_TYPES, R, th, x, dy, mean, invstd, gamma, beta, res, dc_rand,
-                 dc_keep, gt, per_c, N, C, HWv, act, train, dx, dres, dgamma, dbeta);
-#undef E2EP_BN_TYPES
-    return launch_status("e2ep_bn_bwd");
+// ---- template dispatch: f is a generic lambda (integral constants: common.h IntC) -----------
+// f(VEC), VEC = 4 or 1
+template <class F> static void with_vec(bool v4, F f) {
+  if (v4) f(IntC<4>());
+  else f(IntC<1>());
+}
+// f(T, R) for the seven layouts bns_layout() gives
+template <class F> static void with_layout(BnsLayout l, F f) {
+  IntC<BNS_T> t1;
+  IntC<2 * BNS_T> t2;
+  if (l.T == BNS_T && l.R == 1) f(t1, IntC<1>());
+  else if (l.T == BNS_T && l.R == 2) f(t1, IntC<2>());
+  else if (l.T == BNS_T && l.R == 4) f(t1, IntC<4>());
+  else if (l.T == BNS_T) f(t1, IntC<8>());
+  else if (l.R == 1) f(t2, IntC<1>());
+  else if (l.R == 2) f(t2, IntC<2>());
+  else f(t2, IntC<4>());
+}
+// f(x, dy, dx) as typed pointers for the four storage combinations of BnIo
+template <class F> static void with_bn_io(int io, const void *x, const void *dy, void *dx, F f) {
+  const float *xf = static_cast<const float *>(x), *dyf = static_cast<const float *>(dy);
+  const bf16_t *xb = static_cast<const bf16_t *>(x), *dyb = static_cast<const bf16_t *>(dy);
+  if (io == BNIO_XDX) f(xb, dyf, static_cast<bf16_t *>(dx));
+  else if (io == BNIO_ALL) f(xb, dyb, static_cast<bf16_t *>(dx));
+  else if (io == BNIO_DY) f(xf, dyb, static_cast<float *>(dx));
+  else f(xf, dyf, static_cast<float *>(dx));
+}
+template <class P> using elem_t = std::remove_const_t<std::remove_pointer_t<P>>;
+// The entry points refuse bf16 storage unless H * W % 4 == 0, so no VEC = 1 kernel with a bf16
+// storage type is built
+template <int VEC, class... Ts>
+constexpr bool bn_built = VEC == 4 || (std::is_same<Ts, float>::value && ...);
+
+// what the forward kernels share: the statistics' arguments, the elementwise tail
+// y = act(dc(z) + res) (e2ep_bn_stats has none: y null) and the folded affine it writes instead
+struct BnFwd {
+  float eps, momentum;
+  float *running_mean, *running_var, *mean, *invstd;
+  const float *gamma, *beta, *res, *dc_rand;
+  float dc_keep;
+  int act;
+  float *y, *scale, *shift;
+};
+
+// e2ep_bn_fwd and e2ep_bn_stats.  Training: the single launch where the plan takes it, else
+// k_bn_stats into the workspace and the caller's tail (k_bn_apply / k_bn_finalize) on those
+// partial sums.  Eval goes straight to the tail with no partial sums.
+template <typename TX, class Tail>
+static int bn_fwd_run(const char *fn, const BnPlan &p, const TX *x, int train, const BnFwd &a,
+                      void *workspace, hipStream_t s, Tail tail) {
+  const BnGeom &g = p.g;
+  if (train && p.fwd.T) {
+    with_layout(p.fwd, [&](auto t, auto r) {
+      constexpr int T = decltype(t)::value;
+      hipLaunchKernelGGL((k_bn_fwd_small<T, decltype(r)::value, TX>), dim3(g.C), dim3(T), 0, s, x,
+                         g.per_c, a.eps, a.momentum, a.running_mean, a.running_var, a.mean, a.invstd,
+                         a.gamma, a.beta, a.res, a.dc_rand, a.dc_keep, g.N, g.C, g.HWv, a.act, a.y,
+                         a.scale, a.shift);
+    });
+  } else if (train) {
+    double *part = static_cast<double *>(workspace);
+    with_vec(g.v4, [&](auto v) {
+      constexpr int VEC = decltype(v)::value;
+      if constexpr (bn_built<VEC, TX>)
+        hipLaunchKernelGGL((k_bn_stats<VEC, TX>), dim3(g.C, p.sp), dim3(256), 0, s, x, g.N, g.C, g.HWv,
+                           p.sp, p.per, part);
+    });
+    tail(part, p.sp);
+  } else {
+    tail(nullptr, 1);
   }
-  E2EP_REQUIRE(workspace && workspace_bytes >= e2ep_bn_workspace(N, C, H, W), E2EP_EINVAL,
-               "e2ep_bn_bwd: workspace %zu bytes < %zu (e2ep_bn_workspace)", workspace_bytes,
-               e2ep_bn_workspace(N, C, H, W));
-  int sp = bn_splits(per_c, C);
-  const int per = cdiv(totv, sp);
-  sp = cdiv(totv, per);
-  double *part = static_cast<double *>(workspace);
-  if (v4)
-    hipLaunchKernelGGL((k_bn_bwd_reduce<4, TX, TD>), dim3(C, sp), dim3(256), 0, s, x, dy, mean, invstd,
-                       gamma, beta, res, dc_rand, dc_keep, gt, N, C, HWv, sp, per, act, part,
-                       bn_rev_reduce());
-  else
-    hipLaunchKernelGGL((k_bn_bwd_reduce<1, TX, TD>), dim3(C, sp), dim3(256), 0, s, x, dy, mean, invstd,
-                       gamma, beta, res, dc_rand, dc_keep, gt, N, C, HWv, sp, per, act, part,
-                       bn_rev_reduce());
-  if (dx || dres) {
-    const dim3 grid(C, cdiv(totv, APPLY_PER));
-    if (v4)
-      hipLaunchKernelGGL((k_bn_bwd_apply<4, TX, TD, TO>), grid, dim3(256), 0, s, x, dy, mean, invstd,
-                         gamma, beta, res, dc_rand, dc_keep, gt, part, sp, per_c, N, C, HWv, APPLY_PER,
-                         act, train, dx, dres, dgamma, dbeta, nullptr, bn_rev_apply());
-    else
-      hipLaunchKernelGGL((k_bn_bwd_apply<1, TX, TD, TO>), grid, dim3(256), 0, s, x, dy, mean, invstd,
-                         gamma, beta, res, dc_rand, dc_keep, gt, part, sp, per_c, N, C, HWv, APPLY_PER,
-                         act, train, dx, dres, dgamma, dbeta, nullptr, bn_rev_apply());
-  } else if (dgamma || dbeta) {
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(C), dim3(256), 0, s, part, sp, dgamma, dbeta);
-  }
-  return launch_status("e2ep_bn_bwd");
+  return launch_status(fn);
 }
 
+// k_bn_apply over the apply grid: e2ep_bn_fwd's tail (scale / shift null) or e2ep_bn_apply
+static void bn_launch_apply(const BnPlan &p, const float *x, const double *part, int sp,
+                            const BnFwd &a, const float *scale, const float *shift, hipStream_t s) {
+  const BnGeom &g = p.g;
+  with_vec(g.v4, [&](auto v) {
+    hipLaunchKernelGGL((k_bn_apply<decltype(v)::value>), dim3(g.C, p.apply_blocks), dim3(256), 0, s, x,
+                       part, sp, g.per_c, a.eps, a.momentum, a.running_mean, a.running_var, a.mean,
+                       a.invstd, a.gamma, a.beta, a.res, a.dc_rand, a.dc_keep, g.N, g.C, g.HWv,
+                       p.apply_per, a.act, a.y, scale, shift, p.rev_fwd);
+  });
+}
+
+// what the backward kernels share
+struct BnBwd {
+  const float *mean, *invstd, *gamma, *beta, *res, *dc_rand;
+  float dc_keep;
+  BnGate gt;
+  int act, train;
+  float *dres, *dgamma, *dbeta;
+};
+
+// k_bn_bwd_apply over the apply grid: the split backward's second pass (part, sp) or
+// e2ep_bn_bwd_planes (planes)
+static void bn_launch_bwd_apply(const BnPlan &p, int io, const void *x, const void *dy, void *dx,
+                                const BnBwd &a, const double *part, int sp, const double *planes,
+                                hipStream_t s) {
+  const BnGeom &g = p.g;
+  with_vec(g.v4, [&](auto v) {
+    with_bn_io(io, x, dy, dx, [&](auto *xt, auto *dyt, auto *dxt) {
+      constexpr int VEC = decltype(v)::value;
+      using TX = elem_t<decltype(xt)>;
+      using TD = elem_t<decltype(dyt)>;
+      using TO = elem_t<decltype(dxt)>;
+      if constexpr (bn_built<VEC, TX, TD, TO>)
+        hipLaunchKernelGGL((k_bn_bwd_apply<VEC, TX, TD, TO>), dim3(g.C, p.apply_blocks), dim3(256), 0,
+                           s, xt, dyt, a.mean, a.invstd, a.gamma, a.beta, a.res, a.dc_rand, a.dc_keep,
+                           a.gt, part, sp, g.per_c, g.N, g.C, g.HWv, p.apply_per, a.act, a.train, dxt,
+                           a.dres, a.dgamma, a.dbeta, planes, p.rev_apply);
+    });
+  });
+}
+
+}  // namespace e2ep
+
+using namespace e2ep;
+
 extern "C" {
+
+size_t e2ep_bn_workspace(int N, int C, int H, int W) { return bn_plan(bn_geom(N, C, H, W)).workspace; }
+
+// 0 also for N, C, H or W <= 0
+int e2ep_bn_fwd_split(int N, int C, int H, int W) {
+  const BnPlan p = bn_plan(bn_geom(N, C, H, W));
+  return p.g.valid && !p.fwd.T;
+}
+
+int e2ep_bn_bwd_split(int N, int C, int H, int W) {
+  const BnPlan p = bn_plan(bn_geom(N, C, H, W));
+  return p.g.valid && !p.bwd.T;
+}
+
+int e2ep_bn_fwd(const float *x, const float *gamma, const float *beta, const float *res,
+                const float *dc_rand, float dc_keep, float *running_mean, float *running_var,
+                int N, int C, int H, int W, int train, float momentum, float eps, int act,
+                float *mean, float *invstd, float *y, void *workspace, size_t workspace_bytes,
+                void *stream) {
+  const char *fn = "e2ep_bn_fwd";
+  const BnPlan p = bn_plan(bn_geom(N, C, H, W));
+  if (int e = bn_check(fn, p, train != 0, workspace, workspace_bytes)) return e;
+  E2EP_REQUIRE(act >= 0 && act <= 2, E2EP_EINVAL, "e2ep_bn_fwd: act must be 0/1/2");
+  E2EP_REQUIRE(train || (running_mean && running_var), E2EP_EINVAL,
+               "e2ep_bn_fwd: eval needs running stats");
+  E2EP_REQUIRE(!dc_rand || dc_keep > 0.f, E2EP_EINVAL, "e2ep_bn_fwd: drop-connect keep must be > 0");
+  const BnFwd a{eps, momentum, running_mean, running_var, mean, invstd, gamma, beta, res, dc_rand,
+                dc_keep, act, y, nullptr, nullptr};
+  hipStream_t s = as_stream(stream);
+  return bn_fwd_run(fn, p, x, train, a, workspace, s, [&](const double *part, int sp) {
+    bn_launch_apply(p, x, part, sp, a, nullptr, nullptr, s);
+  });
+}
+
+int e2ep_bn_stats(const void *x, const float *gamma, const float *beta, float *running_mean,
+                  float *running_var, int N, int C, int H, int W, int train, float momentum,
+                  float eps, float *mean, float *invstd, float *scale, float *shift,
+                  void *workspace, size_t workspace_bytes, void *stream, int io) {
+  const char *fn = "e2ep_bn_stats";
+  const BnPlan p = bn_plan(bn_geom(N, C, H, W));
+  E2EP_REQUIRE(io == 0 || (io == E2EP_IO_X_BF16 && p.g.HW % 4 == 0), E2EP_EINVAL,
+               "e2ep_bn_stats: storage mask %d not supported (0 or X bf16, H*W %% 4 == 0)", io);
+  if (int e = bn_check(fn, p, train != 0, workspace, workspace_bytes)) return e;
+  E2EP_REQUIRE(train || (running_mean && running_var), E2EP_EINVAL,
+               "e2ep_bn_stats: eval needs running stats");
+  E2EP_REQUIRE(mean && invstd && scale && shift, E2EP_EINVAL, "e2ep_bn_stats: null output");
+  const BnFwd a{eps, momentum, running_mean, running_var, mean, invstd, gamma, beta, nullptr, nullptr,
+                1.f, 0, nullptr, scale, shift};
+  hipStream_t s = as_stream(stream);
+  auto tail = [&](const double *part, int sp) {
+    hipLaunchKernelGGL(k_bn_finalize, dim3(C), dim3(256), 0, s, part, sp, p.g.per_c, eps, momentum,
+                       running_mean, running_var, mean, invstd, gamma, beta, scale, shift);
+  };
+  if (io) return bn_fwd_run(fn, p, static_cast<const bf16_t *>(x), train, a, workspace, s, tail);
+  return bn_fwd_run(fn, p, static_cast<const float *>(x), train, a, workspace, s, tail);
+}
+
+size_t e2ep_bn_finalize_part_workspace(int C, int tiles) {
+  (void)C;
+  (void)tiles;
+  return 0;  // one launch, no workspace (kept in the ABI for a future split plan)
+}
+
+int e2ep_bn_finalize_part(const double *part, int tiles, const float *gamma, const float *beta,
+                          float *running_mean, float *running_var, int N, int C, int H, int W,
+                          float momentum, float eps, float *mean, float *invstd, float *scale,
+                          float *shift, void *workspace, size_t workspace_bytes, void *stream) {
+  const BnGeom g = bn_geom(N, C, H, W);
+  E2EP_REQUIRE(part && tiles > 0 && g.valid && C <= 65535, E2EP_EINVAL,
+               "e2ep_bn_finalize_part: bad arguments");
+  E2EP_REQUIRE(mean && invstd && scale && shift, E2EP_EINVAL, "e2ep_bn_finalize_part: null output");
+  E2EP_REQUIRE(!running_mean == !running_var, E2EP_EINVAL,
+               "e2ep_bn_finalize_part: running_mean / running_var both or neither");
+  (void)workspace;
+  (void)workspace_bytes;
+  hipLaunchKernelGGL(k_bn_finalize_tiles, dim3(cdiv(C, FT_CH)), dim3(FT_CH * FT_GROUPS), 0, as_stream(stream),
+                     part, tiles, C, g.per_c, eps, momentum, running_mean, running_var, mean, invstd,
+                     gamma, beta, scale, shift);
+  return launch_status("e2ep_bn_finalize_part");
+}
+
+int e2ep_bn_apply(const float *x, const float *scale, const float *shift, const float *res,
+                  const float *dc_rand, float dc_keep, int N, int C, int H, int W, int act,
+                  float *y, void *stream) {
+  const char *fn = "e2ep_bn_apply";
+  const bool aligned = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0;
+  const BnPlan p = bn_plan(bn_geom(N, C, H, W, aligned));
+  if (int e = bn_check(fn, p)) return e;
+  E2EP_REQUIRE(x && y && scale && shift && act >= 0 && act <= 2, E2EP_EINVAL,
+               "e2ep_bn_apply: bad arguments");
+  E2EP_REQUIRE(!dc_rand || dc_keep > 0.f, E2EP_EINVAL, "e2ep_bn_apply: drop-connect keep must be > 0");
+  const BnFwd a{0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, res, dc_rand, dc_keep,
+                act, y, nullptr, nullptr};
+  bn_launch_apply(p, x, nullptr, 1, a, scale, shift, as_stream(stream));
+  return launch_status(fn);
+}
 
 int e2ep_bn_bwd(const void *x, const void *dy, const float *mean, const float *invstd,
                 const float *gamma, const float *beta, const float *res, const float *dc_rand,
                 float dc_keep, const float *gate_logit, const float *gate_dpooled, int N, int C,
                 int H, int W, int train, int act, void *dx, float *dgamma, float *dbeta,
                 float *dres, void *workspace, size_t workspace_bytes, void *stream, int io) {
-  E2EP_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && (long long)N * H * W < (1LL << 31),
-               E2EP_EINVAL, "e2ep_bn_bwd: bad shape");
+  const char *fn = "e2ep_bn_bwd";
+  const BnPlan p = bn_plan(bn_geom(N, C, H, W));
+  const BnGeom &g = p.g;
+  if (int e = bn_check(fn, p)) return e;
   E2EP_REQUIRE(!gate_logit == !gate_dpooled, E2EP_EINVAL,
                "e2ep_bn_bwd: gate_logit / gate_dpooled both or neither");
   E2EP_REQUIRE(!dc_rand || dc_keep > 0.f, E2EP_EINVAL, "e2ep_bn_bwd: drop-connect keep must be > 0");
-  E2EP_REQUIRE(bn_io_ok(io) && (io == 0 || (H * W) % 4 == 0), E2EP_EINVAL,
+  E2EP_REQUIRE(bn_io_ok(io) && (io == 0 || g.HW % 4 == 0), E2EP_EINVAL,
                "e2ep_bn_bwd: storage mask %d not supported (0, X|DX, X|DY|DX or DY bf16, "
                "H*W %% 4 == 0)", io);
-  const BnGate gt{gate_logit, gate_dpooled, 1.f / (float)(H * W)};
+  const BnBwd a{mean, invstd, gamma, beta, res, dc_rand, dc_keep,
+                BnGate{gate_logit, gate_dpooled, 1.f / (float)g.HW}, act, train, dres, dgamma, dbeta};
   hipStream_t s = as_stream(stream);
-  if (io == BNIO_XDX)
-    return bn_bwd_impl(static_cast<const bf16_t *>(x), static_cast<const float *>(dy), mean, invstd,
-                       gamma, beta, res, dc_rand, dc_keep, gt, N, C, H, W, train, act,
-                       static_cast<bf16_t *>(dx), dgamma, dbeta, dres, workspace, workspace_bytes, s);
-  if (io == BNIO_ALL)
-    return bn_bwd_impl(static_cast<const bf16_t *>(x), static_cast<const bf16_t *>(dy), mean, invstd,
-                       gamma, beta, res, dc_rand, dc_keep, gt, N, C, H, W, train, act,
-                       static_cast<bf16_t *>(dx), dgamma, dbeta, dres, workspace, workspace_bytes, s);
-  if (io == BNIO_DY)
-    return bn_bwd_impl(static_cast<const float *>(x), static_cast<const bf16_t *>(dy), mean, invstd,
-                       gamma, beta, res, dc_rand, dc_keep, gt, N, C, H, W, train, act,
-                       static_cast<float *>(dx), dgamma, dbeta, dres, workspace, workspace_bytes, s);
-  return bn_bwd_impl(static_cast<const float *>(x), static_cast<const float *>(dy), mean, invstd, gamma,
-                     beta, res, dc_rand, dc_keep, gt, N, C, H, W, train, act, static_cast<float *>(dx),
-                     dgamma, dbeta, dres, workspace, workspace_bytes, s);
-}
-
-int e2ep_bn_bwd_split(int N, int C, int H, int W) {
-  if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-  const int HW = H * W;
-  const bool v4 = (HW & 3) == 0;
-  const int totv = N * (v4 ? HW / 4 : HW);
-  int th = 0;
-  return (v4 && bn_small_enabled() && totv <= g_bns_bwd_max && bns_r(totv, th)) ? 0 : 1;
+  if (p.bwd.T) {
+    with_layout(p.bwd, [&](auto t, auto r) {
+      with_bn_io(io, x, dy, dx, [&](auto *xt, auto *dyt, auto *dxt) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL((k_bn_bwd_small<T, decltype(r)::value, elem_t<decltype(xt)>,
+                                           elem_t<decltype(dyt)>, elem_t<decltype(dxt)>>),
+                           dim3(g.C), dim3(T), 0, s, xt, dyt, a.mean, a.invstd, a.gamma, a.beta, a.res,
+                           a.dc_rand, a.dc_keep, a.gt, g.per_c, g.N, g.C, g.HWv, a.act, a.train, dxt,
+                           a.dres, a.dgamma, a.dbeta);
+      });
+    });
+    return launch_status(fn);
+  }
+  if (int e = bn_check(fn, p, true, workspace, workspace_bytes)) return e;
+  double *part = static_cast<double *>(workspace);
+  with_vec(g.v4, [&](auto v) {
+    with_bn_io(io, x, dy, dx, [&](auto *xt, auto *dyt, auto *) {
+      constexpr int VEC = decltype(v)::value;
+      using TX = elem_t<decltype(xt)>;
+      using TD = elem_t<decltype(dyt)>;
+      if constexpr (bn_built<VEC, TX, TD>)
+        hipLaunchKernelGGL((k_bn_bwd_reduce<VEC, TX, TD>), dim3(g.C, p.sp), dim3(256), 0, s, xt, dyt,
+                           a.mean, a.invstd, a.gamma, a.beta, a.res, a.dc_rand, a.dc_keep, a.gt, g.N,
+                           g.C, g.HWv, p.sp, p.per, a.act, part, p.rev_reduce);
+    });
+  });
+  if (dx || dres)
+    bn_launch_bwd_apply(p, io, x, dy, dx, a, part, p.sp, nullptr, s);
+  else if (dgamma || dbeta)
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(g.C), dim3(256), 0, s, part, p.sp, dgamma, dbeta);
+  return launch_status(fn);
 }
 
 int e2ep_bn_bwd_planes(const void *x, const void *dy, const float *mean, const float *invstd,
                        const float *gamma, const float *beta, const float *gate_logit,
                        const float *gate_dpooled, const double *plane_sums, int N, int C, int H,
                        int W, int act, void *dx, float *dgamma, float *dbeta, void *stream, int io) {
-  E2EP_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && (long long)N * H * W < (1LL << 31),
-               E2EP_EINVAL, "e2ep_bn_bwd_planes: bad shape");
+  const char *fn = "e2ep_bn_bwd_planes";
+  const BnPlan p = bn_plan(bn_geom(N, C, H, W));
+  if (int e = bn_check(fn, p)) return e;
   E2EP_REQUIRE(x && dy && mean && invstd && gate_logit && gate_dpooled && plane_sums && dx,
                E2EP_EINVAL, "e2ep_bn_bwd_planes: null argument");
   E2EP_REQUIRE(act >= 0 && act <= 2, E2EP_EINVAL, "e2ep_bn_bwd_planes: act must be 0/1/2");
-  E2EP_REQUIRE((io == BNIO_F32 || io == BNIO_XDX || io == BNIO_ALL) && (io == 0 || (H * W) % 4 == 0),
+  // (a bf16 mask needs H * W % 4 == 0, so it always runs VEC = 4)
+  E2EP_REQUIRE((io == BNIO_F32 || io == BNIO_XDX || io == BNIO_ALL) && (io == 0 || p.g.HW % 4 == 0),
                E2EP_EINVAL, "e2ep_bn_bwd_planes: storage mask %d not supported (0, X|DX or X|DY|DX "
                "bf16, H*W %% 4 == 0)", io);
-  const BnGate gt{gate_logit, gate_dpooled, 1.f / (float)(H * W)};
-  const int HW = H * W;
-  const long long per_c = (long long)N * HW;
-  const bool v4 = (HW & 3) == 0;
-  const int HWv = v4 ? HW / 4 : HW;
-  const int totv = N * HWv;
-  const dim3 grid(C, cdiv(totv, APPLY_PER));
-  hipStream_t s = as_stream(stream);
-  const float *dyf = static_cast<const float *>(dy);
-  if (io == BNIO_ALL)
-    hipLaunchKernelGGL((k_bn_bwd_apply<4, bf16_t, bf16_t, bf16_t>), grid, dim3(256), 0, s,
-                       static_cast<const bf16_t *>(x), static_cast<const bf16_t *>(dy), mean, invstd,
-                       gamma, beta, nullptr, nullptr, 1.f, gt, nullptr, 1, per_c, N, C, HWv, APPLY_PER,
-                       act, 1, static_cast<bf16_t *>(dx), nullptr, dgamma, dbeta, plane_sums,
-                       bn_rev_apply());
-  else if (io == BNIO_XDX)
-    hipLaunchKernelGGL((k_bn_bwd_apply<4, bf16_t, float, bf16_t>), grid, dim3(256), 0, s,
-                       static_cast<const bf16_t *>(x), dyf, mean, invstd, gamma, beta, nullptr, nullptr,
-                       1.f, gt, nullptr, 1, per_c, N, C, HWv, APPLY_PER, act, 1,
-                       static_cast<bf16_t *>(dx), nullptr, dgamma, dbeta, plane_sums,
-                       bn_rev_apply());
-  else if (v4)
-    hipLaunchKernelGGL(k_bn_bwd_apply<4>, grid, dim3(256), 0, s, static_cast<const float *>(x), dyf, mean,
-                       invstd, gamma, beta, nullptr, nullptr, 1.f, gt, nullptr, 1, per_c, N, C, HWv,
-                       APPLY_PER, act, 1, static_cast<float *>(dx), nullptr, dgamma, dbeta, plane_sums,
-                       bn_rev_apply());
-  else
-    hipLaunchKernelGGL(k_bn_bwd_apply<1>, grid, dim3(256), 0, s, static_cast<const float *>(x), dyf, mean,
-                       invstd, gamma, beta, nullptr, nullptr, 1.f, gt, nullptr, 1, per_c, N, C, HWv,
-                       APPLY_PER, act, 1, static_cast<float *>(dx), nullptr, dgamma, dbeta, plane_sums,
-                       bn_rev_apply());
-  return launch_status("e2ep_bn_bwd_planes");
+  const BnBwd a{mean, invstd, gamma, beta, nullptr, nullptr, 1.f,
+                BnGate{gate_logit, gate_dpooled, 1.f / (float)p.g.HW}, act, 1, nullptr, dgamma, dbeta};
+  bn_launch_bwd_apply(p, io, x, dy, dx, a, nullptr, 1, plane_sums, as_stream(stream));
+  return launch_status(fn);
 }
 
 int e2ep_bn_eval_multi(const long long *table, int n, void *stream) {
@@ -1190,3 +1177,4 @@ int e2ep_act_bwd(const float *x, const float *dy, long long n, int act, float *d
 }
 
 }  // extern "C"
+

@@ -17,6 +17,7 @@
 // depthwise weight gradient repeats k_dw_wgrad_strip's one-split order (what channel counts of
 // 512 and more get, the 16x16 stages' 672 / 960 among them); where that kernel would sum
 // several split slabs per channel (fewer channels) the sums differ in order, not in terms.
+#include "bns_layout.h"
 #include "common.h"
 
 // as bn.hip / dwconv.hip / se.hip: a*b + c fuses within one expression only, so the
@@ -495,17 +496,11 @@ __global__ void __launch_bounds__(T, 4) k_mbconv_mid_bwd(
 }
 
 // The <threads, vectors per thread> layout e2ep_bn_fwd / e2ep_bn_bwd give a channel of totv
-// float4 (bn.hip bns_r + BNS_LAUNCH), so the sums here run in their order: 0 = none taken
-// (the channel is too large, or 8 vectors on 256 threads, which these kernels do not build)
-static int mid_layout(int totv, int &R) {
-  const int per = cdiv(totv, 256);
-  const bool lo = g_tune[TUNE_BNS_WIDE_LO] == 2;
-  R = 0;
-  if (per <= 1) { R = 1; return 256; }
-  if (per <= 2) { R = lo ? 1 : 2; return lo ? 512 : 256; }
-  if (per <= 4) { R = lo ? 2 : 4; return lo ? 512 : 256; }
-  if (per <= 8 && g_tune[TUNE_BNS_WIDE] == 2) { R = 4; return 512; }
-  return 0;
+// float4 (bns_layout.h), so the sums here run in their order: {0, 0} = none taken (the channel
+// is too large, or 8 vectors on 256 threads, which these kernels do not build)
+static BnsLayout mid_layout(int totv) {
+  const BnsLayout l = bns_layout(totv);
+  return l.R == BNS_R ? BnsLayout{0, 0} : l;
 }
 
 }  // namespace e2ep
@@ -539,8 +534,7 @@ int e2ep_mbconv_mid_ok(const int *d) {
   if ((long long)N * MID_HW * MID_HW > 8192) return 0;
   // the separate launches must be the single-launch BatchNorm kernels, whose order this repeats
   if (e2ep_bn_fwd_split(N, C, MID_HW, MID_HW) || e2ep_bn_bwd_split(N, C, MID_HW, MID_HW)) return 0;
-  int R = 0;
-  return mid_layout(N * MID_HWV, R) ? 1 : 0;
+  return mid_layout(N * MID_HWV).T ? 1 : 0;
 }
 
 int e2ep_mbconv_mid_fwd(const float *y0, const float *w, const int *dims, const float *gamma0,
@@ -557,8 +551,8 @@ int e2ep_mbconv_mid_fwd(const float *y0, const float *w, const int *dims, const 
   E2EP_REQUIRE(!running_mean0 == !running_var0 && !running_mean1 == !running_var1, E2EP_EINVAL,
                "e2ep_mbconv_mid_fwd: running_mean / running_var both or neither");
   const int N = dims[0], C = dims[1], K = dims[4];
-  int R = 0;
-  const int T = mid_layout(N * MID_HWV, R);
+  const BnsLayout l = mid_layout(N * MID_HWV);
+  const int T = l.T, R = l.R;
   const MidBnFwd b0{gamma0, beta0, running_mean0, running_var0, stats0, stats0 + C, stats0 + 2 * C,
                     stats0 + 3 * C, eps0, momentum0};
   const MidBnFwd b1{gamma1, beta1, running_mean1, running_var1, stats1, stats1 + C, stats1 + 2 * C,
@@ -581,8 +575,8 @@ int e2ep_mbconv_mid_bwd(const float *gy, const float *gate_logit, const float *g
   E2EP_REQUIRE(gy && gate_logit && gate_dpooled && y1 && y0 && w && stats1 && stats0 && dx && dw,
                E2EP_EINVAL, "e2ep_mbconv_mid_bwd: null argument");
   const int N = dims[0], C = dims[1], K = dims[4];
-  int R = 0;
-  const int T = mid_layout(N * MID_HWV, R);
+  const BnsLayout l = mid_layout(N * MID_HWV);
+  const int T = l.T, R = l.R;
   const MidBnBwd b1{stats1, stats1 + C, gamma1, beta1, dgamma1, dbeta1};
   const MidBnBwd b0{stats0, stats0 + C, gamma0, beta0, dgamma0, dbeta0};
   hipStream_t s = as_stream(stream);

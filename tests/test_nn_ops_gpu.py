@@ -101,6 +101,29 @@ def test_bn_act(train, act, res, shape, bn_path):
     assert int(bnd.num_batches_tracked) == int(bn64.num_batches_tracked)
 
 
+@pytest.mark.parametrize("wide_lo", [1, 2], ids=["key26_1", "key26_2"])
+@pytest.mark.parametrize("wide", [1, 2], ids=["key25_1", "key25_2"])
+@pytest.mark.parametrize("shape", [(4, 3, 16, 16), (257, 3, 2, 2), (8, 3, 16, 16), (27, 3, 19, 4),
+                                   (16, 3, 16, 16), (25, 3, 41, 4), (32, 3, 16, 16), (3, 3, 683, 4)])
+def test_bn_act_layouts(shape, wide, wide_lo):
+    """Every <threads, float4 per thread> layout of the single-launch BN kernels, forward and
+    backward, one vector either side of each switch: channels of 256 / 257, 512 / 513,
+    1024 / 1025 and 2048 / 2049 float4 under e2ep_tune keys 25 and 26 (256 x 1; 256 x 2 or
+    512 x 1; 256 x 4 or 512 x 2; 256 x 8 or 512 x 4; 2049 takes the split kernels).  Swish with
+    a residual; eval runs the split route's apply at the same shapes.  vs fp64, test_bn_act's
+    bounds."""
+    from e2ep_amd import _lib
+    lib = _lib.load()
+    prev = lib.e2ep_tune(25, wide)
+    prev_lo = lib.e2ep_tune(26, wide_lo)
+    try:
+        for train in (True, False):
+            test_bn_act(train, "swish", True, shape, 1)
+    finally:
+        lib.e2ep_tune(26, prev_lo)
+        lib.e2ep_tune(25, prev)
+
+
 @pytest.mark.parametrize("shape", [(8, 24, 16, 16), (6, 10, 5, 7), (16, 136, 8, 8)])
 def test_bn_drop_connect_fused(shape, bn_path):
     """MBConv tail in training: bn2 -> efficientnet-pytorch drop_connect (x / keep *
