@@ -357,6 +357,10 @@ class _Conv2d(torch.autograd.Function):
         x, wt, y = ctx.saved_tensors
         dims = ctx.dims
         N, Cin, H, W, Cout, R, S, P, Q = dims[:9]
+        if gy is None:
+            # only the skip alias was used (set_materialize_grads(False)): y contributes nothing,
+            # so the parameters get no gradient and x gets the alias's gradient as it is
+            return (gskip if ctx.needs_input_grad[0] else None), None, None, None, None, None, None, None
         gy = gy.contiguous()
         s = _lib.stream()
         if ctx.act == 1:  # ReLU gradient mask (y > 0 <=> pre-activation > 0), one e2ep launch
@@ -406,8 +410,6 @@ class _Conv2d(torch.autograd.Function):
                 dx[:, :gc] = dxg
         if fork is not None:
             fork.join()
-        if dx is None and gskip is not None and ctx.needs_input_grad[0]:
-            dx = gskip
         return dx, dw, db, None, None, None, None, None
 
 

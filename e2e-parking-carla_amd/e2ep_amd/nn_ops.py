@@ -1088,7 +1088,7 @@ class _AddDropLN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, gamma, beta, u, seed, p, eps):
         a = a.contiguous()
-        b = b.contiguous()
+        b = b.contiguous() if b is not None else None  # nullable, as e2ep_add_drop_ln_fwd's b
         E = a.shape[-1]
         rows = a.numel() // E
         x = torch.empty_like(a)
@@ -1127,8 +1127,11 @@ class _AddDropLN(torch.autograd.Function):
 def add_drop_layer_norm(a, b, norm, p=0.0, u=None, seed=None):
     """norm(a + dropout_p(b)) for an nn.LayerNorm `norm` over the last dim, one fused op.
     The dropout mask is [u >= p] when uniforms `u` are given, else the counter hash keyed by a
-    device seed (e2ep_amd.rng: this step's pool; graph-capturable, nothing drawn per element)."""
+    device seed (e2ep_amd.rng: this step's pool; graph-capturable, nothing drawn per element).
+    b may be None: norm(a).  A norm without elementwise_affine has no weight / bias (1 / 0)."""
     _dev(a, b)
+    if b is None:
+        p = 0.0
     if p > 0.0 and u is None and seed is None:
         seed = rng.seed(a.device)
     if p == 0.0:
@@ -1301,6 +1304,11 @@ class _InProjQKV(torch.autograd.Function):
         xq2, xkv2, weight = ctx.saved_tensors
         nig = ctx.needs_input_grad
         E = ctx.E
+        if gq is None or gkv is None:
+            # set_materialize_grads(False) is for the skip aliases; a projection nobody reads
+            # would leave its rows of dW / db unwritten
+            raise _lib.E2EPError("in_proj_qkv: the backward needs a gradient at both q and kv "
+                                 f"(got q: {gq is not None}, kv: {gkv is not None})")
         want_b = ctx.has_bias and nig[3]
         dw = torch.empty_like(weight) if nig[2] else None
         db = torch.empty(3 * E, dtype=torch.float32, device=weight.device) if want_b else None
