@@ -43,13 +43,6 @@ constexpr float LOG2E = 1.4426950408889634f;
 #define E2EP_ATT_KG 4
 #endif
 constexpr int FWD_KG = E2EP_ATT_KG;  // keys per online-softmax rescale in the forward
-// lanes per query (forward, dq) / per key (dk, dv) for sequences longer than 16 (the encoder's
-// 256): e2ep_tune key 20 (1 = automatic = 1, or 2 / 4 for A/B; more lanes per query = smaller
-// query tiles, more workgroups)
-static int att_lanes() {
-  const int t = g_tune[TUNE_ATT_LANES];
-  return t == 2 || t == 4 ? t : 1;
-}
 
 // 2^x on the hardware v_exp_f32 (arguments here are <= 0 or -inf; tiny results flush to 0)
 __device__ __forceinline__ float att_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -574,6 +567,56 @@ __global__ void __launch_bounds__(256) k_attn_bwd_d(const float *__restrict__ o,
   Dbuf[t] = Di;
 }
 
+namespace e2ep {
+
+AttnRoute attn_route(const AttnDims &a, const uint8_t *key_pad) {
+  const int mf_tune = g_tune[TUNE_ATT_MF], lanes_tune = g_tune[TUNE_ATT_LANES];
+  const bool mf = mf_tune >= 2 && (a.Sq == 128 || a.Sq == 256) && (a.Sk == 128 || a.Sk == 256) &&
+                  a.dh <= 44 && !a.causal && !key_pad;  // 44: attn_mf.hip's 2 * MF_T
+  const int BH = a.B * a.H;
+  // a vector-kernel pass with one query (or key) of a sequence of S per `lanes` lanes
+  auto vec = [&](int S) {
+    const int lanes = S <= 16 || lanes_tune == 4 ? 4 : lanes_tune == 2 ? 2 : 1;
+    return AttnPass{ATT_VEC, a.dh <= 44 ? 44 : 64, lanes, 0, dim3(cdiv(S, 64 / lanes), BH)};
+  };
+  // a matrix-core pass: 32 rows of a sequence of S per block, the other sequence (T) staged whole
+  auto mfp = [&](int S, int T) { return AttnPass{ATT_MF, 0, 0, T / 128, dim3(S / 32, BH)}; };
+  AttnRoute r{};
+  r.fwd = mf ? mfp(a.Sq, a.Sk) : vec(a.Sq);
+  r.d = vec(a.Sq);  // either family's dk / dv reads this D
+  r.d.grid = dim3(cdiv(BH * a.Sq, 256));
+  r.dq = r.fwd;
+  r.dkv = mf && mf_tune == 3 ? mfp(a.Sk, a.Sq) : vec(a.Sk);
+  for (int avg = 0; avg < 2; ++avg) {
+    r.w[avg] = r.d;
+    r.w[avg].family = r.fwd.family;
+    const int rows = avg ? a.B : BH;  // the head mean sums the heads inside a block
+    r.w[avg].grid = mf ? dim3((a.Sq / 32) * (a.Sk / 128), rows)
+                       : dim3(cdiv(a.Sq, avg ? ATT_W_QT_AVG : ATT_W_QT), rows);
+  }
+  // 0 in order on one stream; 2 and 3 after 1, independent of each other (two streams)
+  r.part[0] = AttnBwdPart{false, true, true, true}, r.part[1] = AttnBwdPart{true, false, false, false};
+  r.part[2] = AttnBwdPart{false, true, false, false}, r.part[3] = AttnBwdPart{false, false, false, true};
+  return r;
+}
+
+// ---- template dispatch of the ATT_VEC passes: f is a generic lambda (common.h IntC) ---------
+// f(DHP)
+template <class F> static void with_dhp(const AttnPass &ps, F f) {
+  if (ps.dhp == 44) f(IntC<44>());
+  else f(IntC<64>());
+}
+// f(DHP, LANES)
+template <class F> static void with_dhp_lanes(const AttnPass &ps, F f) {
+  with_dhp(ps, [&](auto dhp) {
+    if (ps.lanes == 4) f(dhp, IntC<4>());
+    else if (ps.lanes == 2) f(dhp, IntC<2>());
+    else f(dhp, IntC<1>());
+  });
+}
+
+}  // namespace e2ep
+
 extern "C" {
 
 int e2ep_attn_fwd(const float *q, const float *k, const float *v, int B, int H, int Sq, int Sk,
@@ -584,21 +627,14 @@ int e2ep_attn_fwd(const float *q, const float *k, const float *v, int B, int H, 
   if (int rc = attn_check(a, "e2ep_attn_fwd")) return rc;
   E2EP_REQUIRE(p == 0.f || seed, E2EP_EINVAL, "e2ep_attn_fwd: dropout needs a seed");
   hipStream_t st = as_stream(stream);
-  if (attn_mf_ok(a, key_pad)) {  // the fusion encoder's 256-token self-attention (attn_mf.hip)
-    attn_mf_fwd(q, k, v, seed, a, o, lse, st);
-    return launch_status("e2ep_attn_fwd");
-  }
-  const dim3 blk(ATT_WAVES * 64);
-  // short query sequences (the control decoder's 14 tokens): 4 lanes per query
-#define E2EP_ATT_FWD(DHP, LPQ)                                                                   \
-  hipLaunchKernelGGL((k_attn_fwd<DHP, LPQ>), dim3(cdiv(Sq, 64 / LPQ), B * H), blk, 0, st, q, k, v, \
-                     key_pad, seed, a, o, lse)
-  if (dh <= 44) {
-    if (Sq <= 16 || att_lanes() == 4) E2EP_ATT_FWD(44, 4); else if (att_lanes() == 2) E2EP_ATT_FWD(44, 2); else E2EP_ATT_FWD(44, 1);
-  } else {
-    if (Sq <= 16 || att_lanes() == 4) E2EP_ATT_FWD(64, 4); else if (att_lanes() == 2) E2EP_ATT_FWD(64, 2); else E2EP_ATT_FWD(64, 1);
-  }
-#undef E2EP_ATT_FWD
+  const AttnPass ps = attn_route(a, key_pad).fwd;
+  if (ps.family == ATT_MF)
+    attn_mf_fwd(ps, q, k, v, seed, a, o, lse, st);
+  else
+    with_dhp_lanes(ps, [&](auto dhp, auto lpq) {
+      hipLaunchKernelGGL((k_attn_fwd<decltype(dhp)::value, decltype(lpq)::value>), ps.grid,
+                         dim3(ATT_WAVES * 64), 0, st, q, k, v, key_pad, seed, a, o, lse);
+    });
   return launch_status("e2ep_attn_fwd");
 }
 
@@ -610,20 +646,19 @@ int e2ep_attn_weights(const float *q, const float *k, const float *lse, int B, i
   E2EP_REQUIRE(q && k && lse && w, E2EP_EINVAL, "e2ep_attn_weights: null q / k / lse / w");
   E2EP_REQUIRE(average == 0 || average == 1, E2EP_EINVAL, "e2ep_attn_weights: average must be 0 or 1");
   hipStream_t st = as_stream(stream);
-  if (attn_mf_ok(a, key_pad)) {  // the fusion encoder's shape (attn_mf.hip)
-    attn_mf_weights(q, k, lse, a, average, w, st);
-    return launch_status("e2ep_attn_weights");
-  }
-  const dim3 blk(ATT_WAVES * 64);
-  const dim3 grid = average ? dim3(cdiv(Sq, ATT_W_QT_AVG), B) : dim3(cdiv(Sq, ATT_W_QT), B * H);
-#define E2EP_ATT_W(DHP, AVG) \
-  hipLaunchKernelGGL((k_attn_w<DHP, AVG>), grid, blk, 0, st, q, k, lse, key_pad, a, w)
-  if (dh <= 44) {
-    if (average) E2EP_ATT_W(44, true); else E2EP_ATT_W(44, false);
-  } else {
-    if (average) E2EP_ATT_W(64, true); else E2EP_ATT_W(64, false);
-  }
-#undef E2EP_ATT_W
+  const AttnPass ps = attn_route(a, key_pad).w[average];
+  if (ps.family == ATT_MF)
+    attn_mf_weights(ps, q, k, lse, a, average, w, st);
+  else
+    with_dhp(ps, [&](auto dhp) {
+      constexpr int DHP = decltype(dhp)::value;
+      if (average)
+        hipLaunchKernelGGL((k_attn_w<DHP, true>), ps.grid, dim3(ATT_WAVES * 64), 0, st, q, k, lse,
+                           key_pad, a, w);
+      else
+        hipLaunchKernelGGL((k_attn_w<DHP, false>), ps.grid, dim3(ATT_WAVES * 64), 0, st, q, k, lse,
+                           key_pad, a, w);
+    });
   return launch_status("e2ep_attn_weights");
 }
 
@@ -641,43 +676,27 @@ int e2ep_attn_bwd_part(const float *q, const float *k, const float *v, const flo
   float *D = static_cast<float *>(workspace);
   hipStream_t s = as_stream(stream);
   const dim3 blk(ATT_WAVES * 64);
-#define E2EP_ATT_BQ(DHP, LPQ, DB)                                                                \
-  hipLaunchKernelGGL((k_attn_bwd_q<DHP, LPQ>), dim3(cdiv(Sq, 64 / LPQ), B * H), blk, 0, s, q, k, v, \
-                     o, dout, lse, key_pad, seed, a, dq, DB)
-#define E2EP_ATT_BKV(DHP, LPK)                                                                   \
-  hipLaunchKernelGGL((k_attn_bwd_kv<DHP, LPK>), dim3(cdiv(Sk, 64 / LPK), B * H), blk, 0, s, q, k, \
-                     v, dout, lse, D, key_pad, seed, a, dk, dv)
-  // part 0: everything in order; 1: D only; 2: dq only (D already in the workspace); 3: dk, dv
-  // only (likewise) — parts 2 and 3 are independent and may run on two streams
-  if (part == 1) {
-    if (dh <= 44)
-      hipLaunchKernelGGL(k_attn_bwd_d<44>, dim3(cdiv(B * H * Sq, 256)), dim3(256), 0, s, o, dout, a, D);
-    else
-      hipLaunchKernelGGL(k_attn_bwd_d<64>, dim3(cdiv(B * H * Sq, 256)), dim3(256), 0, s, o, dout, a, D);
-    return launch_status("e2ep_attn_bwd");
-  }
-  float *Dq = part == 2 ? nullptr : D;  // dq pass alone: D is read by the other pass, not rewritten
-  if (attn_mf_ok(a, key_pad)) {  // matrix-core dq (+ D) (attn_mf.hip); dk / dv below or there
-    if (attn_mf_bwd(q, k, v, o, dout, lse, seed, a, dq, dk, dv, D, part, s) || part == 2)
-      return launch_status("e2ep_attn_bwd");
-    part = 3;  // dk / dv on the vector-FMA kernel (faster at this shape), reading D
-  }
-  if (part != 3) {
-    if (dh <= 44) {
-      if (Sq <= 16 || att_lanes() == 4) E2EP_ATT_BQ(44, 4, Dq); else if (att_lanes() == 2) E2EP_ATT_BQ(44, 2, Dq); else E2EP_ATT_BQ(44, 1, Dq);
-    } else {
-      if (Sq <= 16 || att_lanes() == 4) E2EP_ATT_BQ(64, 4, Dq); else if (att_lanes() == 2) E2EP_ATT_BQ(64, 2, Dq); else E2EP_ATT_BQ(64, 1, Dq);
-    }
-  }
-  if (part != 2) {
-    if (dh <= 44) {
-      if (Sk <= 16 || att_lanes() == 4) E2EP_ATT_BKV(44, 4); else if (att_lanes() == 2) E2EP_ATT_BKV(44, 2); else E2EP_ATT_BKV(44, 1);
-    } else {
-      if (Sk <= 16 || att_lanes() == 4) E2EP_ATT_BKV(64, 4); else if (att_lanes() == 2) E2EP_ATT_BKV(64, 2); else E2EP_ATT_BKV(64, 1);
-    }
-  }
-#undef E2EP_ATT_BQ
-#undef E2EP_ATT_BKV
+  const AttnRoute r = attn_route(a, key_pad);
+  const AttnBwdPart run = r.part[part];
+  if (run.d)
+    with_dhp(r.d, [&](auto dhp) {
+      hipLaunchKernelGGL(k_attn_bwd_d<decltype(dhp)::value>, r.d.grid, dim3(256), 0, s, o, dout, a, D);
+    });
+  float *Dw = run.dq_writes_d ? D : nullptr;
+  if (run.dq && r.dq.family == ATT_MF)
+    attn_mf_bq(r.dq, q, k, v, o, dout, lse, seed, a, dq, Dw, s);
+  else if (run.dq)
+    with_dhp_lanes(r.dq, [&](auto dhp, auto lpq) {
+      hipLaunchKernelGGL((k_attn_bwd_q<decltype(dhp)::value, decltype(lpq)::value>), r.dq.grid, blk,
+                         0, s, q, k, v, o, dout, lse, key_pad, seed, a, dq, Dw);
+    });
+  if (run.dkv && r.dkv.family == ATT_MF)
+    attn_mf_bkv(r.dkv, q, k, v, dout, lse, D, seed, a, dk, dv, s);
+  else if (run.dkv)
+    with_dhp_lanes(r.dkv, [&](auto dhp, auto lpk) {
+      hipLaunchKernelGGL((k_attn_bwd_kv<decltype(dhp)::value, decltype(lpk)::value>), r.dkv.grid, blk,
+                         0, s, q, k, v, dout, lse, D, key_pad, seed, a, dk, dv);
+    });
   return launch_status("e2ep_attn_bwd");
 }
 

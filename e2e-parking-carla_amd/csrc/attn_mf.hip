@@ -416,49 +416,45 @@ __global__ void __launch_bounds__(256) k_attn_w_mf(const float *__restrict__ q,
   }
 }
 
-void attn_mf_weights(const float *q, const float *k, const float *lse2, const AttnDims &a,
-                     int average, float *w, hipStream_t s) {
-  const int tiles = (a.Sq / 32) * (a.Sk / 128);
+// ---- launches of the ATT_MF passes of attn_route (attn.hip): ps.nt and ps.grid from there ----
+// f(NT)
+template <class F> static void with_nt(const AttnPass &ps, F f) {
+  if (ps.nt == 2) f(IntC<2>());
+  else f(IntC<1>());
+}
+
+void attn_mf_fwd(const AttnPass &ps, const float *q, const float *k, const float *v,
+                 const int *seed, const AttnDims &a, float *o, float *lse2, hipStream_t s) {
+  with_nt(ps, [&](auto nt) {
+    hipLaunchKernelGGL(k_attn_fwd_mf<decltype(nt)::value>, ps.grid, dim3(256), 0, s, q, k, v, seed, a,
+                       o, lse2);
+  });
+}
+
+void attn_mf_bq(const AttnPass &ps, const float *q, const float *k, const float *v, const float *o,
+                const float *dout, const float *lse2, const int *seed, const AttnDims &a,
+                float *dq, float *Dw, hipStream_t s) {
+  with_nt(ps, [&](auto nt) {
+    hipLaunchKernelGGL(k_attn_bq_mf<decltype(nt)::value>, ps.grid, dim3(256), 0, s, q, k, v, o, dout,
+                       lse2, seed, a, dq, Dw);
+  });
+}
+
+void attn_mf_bkv(const AttnPass &ps, const float *q, const float *k, const float *v,
+                 const float *dout, const float *lse2, const float *Dbuf, const int *seed,
+                 const AttnDims &a, float *dk, float *dv, hipStream_t s) {
+  with_nt(ps, [&](auto nt) {
+    hipLaunchKernelGGL(k_attn_bkv_mf<decltype(nt)::value>, ps.grid, dim3(256), 0, s, q, k, v, dout,
+                       lse2, Dbuf, seed, a, dk, dv);
+  });
+}
+
+void attn_mf_weights(const AttnPass &ps, const float *q, const float *k, const float *lse2,
+                     const AttnDims &a, int average, float *w, hipStream_t s) {
   if (average)
-    hipLaunchKernelGGL(k_attn_w_mf<true>, dim3(tiles, a.B), dim3(256), 0, s, q, k, lse2, a, w);
+    hipLaunchKernelGGL(k_attn_w_mf<true>, ps.grid, dim3(256), 0, s, q, k, lse2, a, w);
   else
-    hipLaunchKernelGGL(k_attn_w_mf<false>, dim3(tiles, a.B * a.H), dim3(256), 0, s, q, k, lse2, a, w);
-}
-
-bool attn_mf_ok(const AttnDims &a, const uint8_t *key_pad) {
-  if (g_tune[TUNE_ATT_MF] <= 1) return false;
-  const bool s_ok = (a.Sq == 128 || a.Sq == 256) && (a.Sk == 128 || a.Sk == 256);
-  return s_ok && a.dh <= 2 * MF_T && !a.causal && !key_pad;
-}
-
-void attn_mf_fwd(const float *q, const float *k, const float *v, const int *seed,
-                 const AttnDims &a, float *o, float *lse2, hipStream_t s) {
-  const dim3 grid(a.Sq / 32, a.B * a.H);
-  if (a.Sk == 256)
-    hipLaunchKernelGGL(k_attn_fwd_mf<2>, grid, dim3(256), 0, s, q, k, v, seed, a, o, lse2);
-  else
-    hipLaunchKernelGGL(k_attn_fwd_mf<1>, grid, dim3(256), 0, s, q, k, v, seed, a, o, lse2);
-}
-
-bool attn_mf_bwd(const float *q, const float *k, const float *v, const float *o,
-                 const float *dout, const float *lse2, const int *seed, const AttnDims &a,
-                 float *dq, float *dk, float *dv, float *Dbuf, int part, hipStream_t s) {
-  if (part != 3) {
-    const dim3 grid(a.Sq / 32, a.B * a.H);
-    float *Dw = part == 0 ? Dbuf : nullptr;
-    if (a.Sk == 256)
-      hipLaunchKernelGGL(k_attn_bq_mf<2>, grid, dim3(256), 0, s, q, k, v, o, dout, lse2, seed, a, dq, Dw);
-    else
-      hipLaunchKernelGGL(k_attn_bq_mf<1>, grid, dim3(256), 0, s, q, k, v, o, dout, lse2, seed, a, dq, Dw);
-  }
-  if (part != 2 && g_tune[TUNE_ATT_MF] == 3) {  // dk / dv on the matrix cores only when asked
-    const dim3 grid(a.Sk / 32, a.B * a.H);
-    if (a.Sq == 256)
-      hipLaunchKernelGGL(k_attn_bkv_mf<2>, grid, dim3(256), 0, s, q, k, v, dout, lse2, Dbuf, seed, a, dk, dv);
-    else
-      hipLaunchKernelGGL(k_attn_bkv_mf<1>, grid, dim3(256), 0, s, q, k, v, dout, lse2, Dbuf, seed, a, dk, dv);
-  }
-  return part != 2 && g_tune[TUNE_ATT_MF] == 3;
+    hipLaunchKernelGGL(k_attn_w_mf<false>, ps.grid, dim3(256), 0, s, q, k, lse2, a, w);
 }
 
 }  // namespace e2ep

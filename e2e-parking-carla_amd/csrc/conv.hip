@@ -1708,17 +1708,21 @@ static int conv1x1_gemm(int mode, int act, const float *w, const float *src, con
                         hipStream_t s) {
   const int HW = g.H * g.W;
   const int N = g.N * HW;
-  const long long w_bytes = 4LL * g.Cout * g.Cin;
+  const int K = mode == 0 ? g.Cin : g.Cout;  // channels summed over = src's channels
+  GemmProblem q{};
+  q.A = w, q.lda = g.Cin, q.a_bytes = 4LL * g.Cout * g.Cin;
+  q.B = src, q.ldb = HW, q.b_bytes = 4LL * g.N * K * HW;
+  q.C = dst, q.ldc = HW, q.c_bytes = dst_bytes;
+  q.cols = GemmCols{HW, (long long)K * HW, (long long)M * HW};
+  q.M = M, q.N = N, q.K = K;
   if (mode == 0) {  // y[n][co][p] = sum_ci w[co][ci] x[n][ci][p] (+ bias[co]) (relu)
-    return gemm_run(w, g.Cin, true, w_bytes, src, HW, false, 4LL * g.N * g.Cin * HW, bias, true,
-                    nullptr, 0, dst, dst_bytes, HW, GemmCols{HW, (long long)g.Cin * HW, (long long)M * HW},
-                    M, N, g.Cin, act == 1, workspace, s);
+    q.ak = true;
+    q.bias = bias, q.bias_rows = true;
+    q.relu = act == 1;
+  } else {  // dx[n][ci][p] = sum_co w[co][ci] gout[n][co][p] (+ res[n][ci][p])
+    q.Cadd = bias, q.ldadd = HW;
   }
-  // dx[n][ci][p] = sum_co w[co][ci] gout[n][co][p] (+ res[n][ci][p])
-  return gemm_run(w, g.Cin, false, w_bytes, src, HW, false, 4LL * g.N * g.Cout * HW, nullptr,
-                  false, bias, HW, dst, dst_bytes, HW,
-                  GemmCols{HW, (long long)g.Cout * HW, (long long)M * HW}, M, N, g.Cout, 0,
-                  workspace, s);
+  return gemm_run(q, workspace, s);
 }
 
 // weight-gradient kernel family: k_wgrad_lp for C3 (bf16 operands; fp16 inference keeps the fp32

@@ -13,11 +13,31 @@ struct GemmCols {
   long long b_img, c_img;
 };
 
-// C = A B (+ bias: per column, or per row when bias_rows) (+ Cadd) (ReLU); see gemm.hip.
-int gemm_run(const float *A, int lda, bool ak, long long a_bytes, const float *B, int ldb,
-             bool bk, long long b_bytes, const float *bias, bool bias_rows, const float *Cadd,
-             int ldadd, float *C, long long c_bytes, int ldc, GemmCols cols, int M, int N, int K,
-             int relu, void *workspace, hipStream_t s, float *rs = nullptr);
+// One product C = A B (+ bias: per column, or per row when bias_rows) (+ Cadd) (ReLU); see
+// gemm.hip.  Filled by name (GemmProblem q{}; q.A = ...): what is left out is absent.
+struct GemmProblem {
+  const float *A;  // A(m, k) = ak ? A[m * lda + k] : A[k * lda + m]
+  int lda;
+  bool ak;
+  long long a_bytes;  // bytes from the base to the end of the last element, as b_bytes, c_bytes
+  const float *B;  // B(k, n) = bk ? B[n * ldb + k] : B[k * ldb + n]
+  int ldb;
+  bool bk;
+  long long b_bytes;
+  const float *bias;
+  bool bias_rows;
+  const float *Cadd;
+  int ldadd;
+  float *C;
+  int ldc;
+  long long c_bytes;
+  GemmCols cols;
+  int M, N, K, relu;
+  float *rs;  // rs[m] = sum_k A(m, k) from the same launch (needs !ak, !bk, unbatched C)
+};
+
+int gemm_run(const GemmProblem &q, void *workspace, hipStream_t s);
+// split-K workspace bytes of an M x N x K product (any layout)
 size_t gemm_ws(int M, int N, int K);
 
 }  // namespace e2ep

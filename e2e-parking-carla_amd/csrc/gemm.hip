@@ -515,9 +515,8 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(
   }
 }
 
-struct GemmLaunch {
-  int tile, splits, kper;
-};
+// ---- host: one plan per product (gemm_plan), one dispatcher family, one entry check ----------
+namespace {  // (conv.hip has a GemmPlan of its own for its implicit GEMMs)
 
 // Block tiles (wm waves along M, wave tile 32 tm x 32 tn):
 //   1: 64 x 64 (2 x 2 waves, 32 x 32)     2: 32 x 128 (1 x 4, 32 x 32)
@@ -528,219 +527,251 @@ struct GemmLaunch {
 struct GemmTile {
   int bm, bn;
 };
-static GemmTile tile_dims(int tile) {
-  switch (tile) {
-    case 2: return {32, 128};
-    case 3: return {128, 128};
-    case 4: return {64, 128};
-    case 5: return {128, 64};
-    case 6: return {64, 256};
-    default: return {64, 64};
-  }
+GemmTile tile_dims(int tile) {
+  const GemmTile dims[7] = {{64, 64}, {64, 64}, {32, 128}, {128, 128}, {64, 128}, {128, 64}, {64, 256}};
+  return dims[tile >= 1 && tile <= 6 ? tile : 1];
 }
 
-// Automatic plan (scripts/bench_gemm.py --sweep / --conv): 64 x 64, or 32 x 128 when M is not
-// a multiple of 64 and 32-row tiles pad it less (M = 32, 112, 144, 160, 336 ...); K split
-// toward ~768 workgroups (3 per CU), at most 8 ways and >= 8 K-steps each.
-static int g_force_tile = 0, g_force_splits = 0;  // 0: automatic
+// The process-wide settings below and e2ep_tune keys 4 and 28 are read by gemm_plan alone.
+int g_force_tile = 0, g_force_splits = 0;  // e2ep_gemm_force; 0: automatic
 // K-steps per split for grids under 64 blocks (e2ep_gemm_split_min).  8, 4 and 2 measured
 // the same C2 step within noise (25.52 / 25.49 / 25.44 ms, profiles/r02/session6/
 // gemm_split_min_ab.txt): the default stays 8.
-static int g_split_min_small = 8;
+int g_split_min_small = 8;
 // e2ep_gemm_skinny: few-row forward products up to this M.  16 (the decoder at B = 1): C5
 // predict fp16 4.84 -> 4.28 ms p50; the C2 step's 112-row decoder measured slower on it (25.66
 // vs 25.39 ms/step, profiles/r02/session6/skinny_ab.txt), so it stays on the MFMA tiles.
-static int g_skinny_rows = 16;
+int g_skinny_rows = 16;
 // operand precision of k_gemm (e2ep_gemm_precision): 0 fp32, 1 bf16 (C3)
-static int g_gemm_precision = 0;
-
-static GemmLaunch gemm_plan(int M, int N, int K) {
-  GemmLaunch p{1, 1, 1};
-  const int ksteps = cdiv(K, G_BK);
-  if (g_force_tile > 0) {  // benchmarking override (e2ep_gemm_force)
-    p.tile = g_force_tile;
-    p.splits = std::max(1, std::min(g_force_splits, ksteps));
-  } else {
-    if (cdiv(M, 32) * 32 < cdiv(M, 64) * 64) p.tile = 2;
-    const GemmTile t = tile_dims(p.tile);
-    const long long blocks = (long long)cdiv(M, t.bm) * cdiv(N, t.bn);
-    // tiny grids (the decoder's 112-row products: a dozen blocks) are a chain of K-steps, so
-    // they may split down to g_split_min_small steps per split (e2ep_gemm_split_min)
-    const long long nb = (long long)cdiv(M, t.bm) * cdiv(N, t.bn);
-    const int smin = nb < 64 ? g_split_min_small : 8;
-    const int cap = std::min(nb < 64 ? 16 : 8, std::max(1, ksteps / smin));
-    p.splits = (int)std::min<long long>(cap, std::max(1LL, (long long)cdiv(g_tune[TUNE_GEMM_SPLIT_TARGET], blocks)));
-  }
-  p.kper = cdiv(ksteps, p.splits);
-  p.splits = cdiv(ksteps, p.kper);
-  return p;
-}
-
-size_t gemm_ws(int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const GemmLaunch p = gemm_plan(M, N, K);
-  return p.splits > 1 ? (size_t)p.splits * M * N * sizeof(float) : 0;
-}
+int g_gemm_precision = 0;
 
 // vector loads along k for k-contiguous operands: 2 = float4 (rows 16-byte aligned), 1 =
 // float2 (8-byte aligned: the d = 258 rows).  Row-contiguous operands stay on dword loads
 // (lanes consecutive along the row): a float2 row-pair variant measured 1.2 - 1.5x slower on
 // the weight-gradient shapes.
-static int vec_of(bool kc, int ld, const void *ptr) {
+int vec_of(bool kc, int ld, const void *ptr) {
   if (!kc) return 0;
   if (ld % 4 == 0 && ((uintptr_t)ptr & 15) == 0) return 2;
   return ld % 2 == 0 && ((uintptr_t)ptr & 7) == 0 ? 1 : 0;
 }
 
-static bool skinny_ok(bool ak, bool bk, bool bias_rows, GemmCols cols, int M, float *rs) {
-  return ak && bk && !bias_rows && cols.hw == 0 && !rs && M <= g_skinny_rows && g_force_tile == 0;
+enum GemmRoute {
+  GEMM_SKINNY,  // k_gemm_skinny<skinny_v>; the tile fields below are still filled (ws_bytes)
+  GEMM_TILES,   // k_gemm, one split, epilogue in the launch
+  GEMM_FOLD,    // k_gemm, K split, the last-arriving split of a tile folds (e2ep_tune key 28 = 2)
+  GEMM_REDUCE,  // k_gemm, K split, then k_gemm_reduce<reduce_v>
+};
+
+struct GemmPlan {  // everything the host decides about one product, decided once by gemm_plan()
+  GemmRoute route;
+  int op;    // operand precision of k_gemm (the skinny kernel stays fp32)
+  int tile;  // 1..6; bf16 operands: a forced 3..6 runs as 1 (clamped after the splits are set)
+  int nx;    // logical columns planned for: N + 1 with a row sum (the ones column)
+  // Automatic: toward e2ep_tune key 4 workgroups, at most 8 ways and >= 8 K-steps each; grids
+  // under 64 blocks (the decoder's 112-row products: a chain of K-steps on a dozen blocks) at
+  // most 16 ways and >= e2ep_gemm_split_min K-steps.  Forced splits are clamped to the K-step
+  // count.  Then rebalanced, kper = ceil(ksteps / splits), splits = ceil(ksteps / kper): no
+  // split is empty (a forced 3 over 4 K-steps runs as 2).
+  int splits, kper;
+  int gx, gy;  // column tiles x row tiles (x splits = the k_gemm grid)
+  // Split-K partials, splits * M * nx floats (0 unsplit): a function of the splits alone, so
+  // neither precision nor fold mode changes it.  Filled on the skinny route too, which never
+  // touches a workspace: e2ep_gemm_workspace knows no layout, and e2ep_gemm demands what it says.
+  size_t ws_bytes;
+  int avec, bvec;  // vec_of each operand (0 for a row-contiguous one)
+  int skinny_v;    // 2: float2 along k (lda, ldb even, A and B 8-byte aligned), else 1
+  int reduce_v;    // 4: float4 reduce (dense C and Cadd, column bias, no row sum, 16-byte C), else 1
+  // Can be half of a k_gemm_pair launch: an automatic plan (tile 1 or 2) that is unsplit or
+  // folds in the launch.  A pair needs both halves pairable and, for each split half, counters.
+  bool pairable;
+};
+
+GemmPlan gemm_plan(const GemmProblem &q) {
+  GemmPlan p{};
+  const bool forced = g_force_tile > 0;  // benchmarking override (e2ep_gemm_force)
+  const int M = q.M, ksteps = cdiv(q.K, G_BK);
+  p.op = g_gemm_precision;
+  p.nx = q.rs ? q.N + 1 : q.N;
+  // automatic: 32 x 128 when 32-row tiles pad M less than 64-row ones (M = 32, 112, 144, 160,
+  // 336 ...), else 64 x 64 (scripts/bench_gemm.py --sweep / --conv)
+  p.tile = forced ? g_force_tile : cdiv(M, 32) * 32 < cdiv(M, 64) * 64 ? 2 : 1;
+  if (forced) {
+    p.splits = std::max(1, std::min(g_force_splits, ksteps));
+  } else {
+    const GemmTile t = tile_dims(p.tile);
+    const long long blocks = (long long)cdiv(M, t.bm) * cdiv(p.nx, t.bn);
+    const int smin = blocks < 64 ? g_split_min_small : 8;
+    const int cap = std::min(blocks < 64 ? 16 : 8, std::max(1, ksteps / smin));
+    p.splits = (int)std::min<long long>(
+        cap, std::max(1LL, (long long)cdiv(g_tune[TUNE_GEMM_SPLIT_TARGET], blocks)));
+  }
+  p.kper = cdiv(ksteps, p.splits);
+  p.splits = cdiv(ksteps, p.kper);
+  if (p.op == 1 && p.tile != 1 && p.tile != 2) p.tile = 1;
+  const GemmTile t = tile_dims(p.tile);
+  p.gx = cdiv(p.nx, t.bn), p.gy = cdiv(M, t.bm);
+  p.ws_bytes = p.splits > 1 ? (size_t)p.splits * M * p.nx * sizeof(float) : 0;
+  const bool skinny = q.ak && q.bk && !q.bias_rows && q.cols.hw == 0 && !q.rs && M <= g_skinny_rows && !forced;
+  p.route = skinny ? GEMM_SKINNY : p.splits == 1 ? GEMM_TILES
+            : g_tune[TUNE_SPLITK_FOLD] == 2 ? GEMM_FOLD : GEMM_REDUCE;
+  p.avec = vec_of(q.ak, q.lda, q.A), p.bvec = vec_of(q.bk, q.ldb, q.B);
+  p.skinny_v = q.lda % 2 == 0 && q.ldb % 2 == 0 && (((uintptr_t)q.A | (uintptr_t)q.B) & 7) == 0 ? 2 : 1;
+  p.reduce_v = !q.rs && (long long)M * q.N % 4 == 0 && q.ldc == q.N && q.cols.hw == 0 &&
+                       !q.bias_rows && (!q.Cadd || q.ldadd == q.N) && ((uintptr_t)q.C & 15) == 0
+                   ? 4 : 1;
+  p.pairable = !forced && (p.tile == 1 || p.tile == 2) && p.route != GEMM_SKINNY && p.route != GEMM_REDUCE;
+  return p;
 }
 
-int gemm_run(const float *A, int lda, bool ak, long long a_bytes, const float *B, int ldb,
-             bool bk, long long b_bytes, const float *bias, bool bias_rows, const float *Cadd,
-             int ldadd, float *C, long long c_bytes, int ldc, GemmCols cols, int M, int N, int K,
-             int relu, void *workspace, hipStream_t s, float *rs) {
-  if (rs && (ak || bk || cols.hw)) {
-    set_error("gemm: the row sum of A needs a k-major A, a row-contiguous B, unbatched C");
-    return E2EP_EINVAL;
+GemmArgs gemm_args(const GemmProblem &q, const GemmPlan &p, void *workspace, unsigned int *cnt) {
+  return GemmArgs{q.A, q.lda, q.a_bytes, q.B, q.ldb, q.b_bytes, q.bias, q.bias_rows ? 1 : 0,
+                  q.Cadd, q.ldadd, q.C, q.c_bytes, q.ldc, q.cols, q.M, q.N, q.K, p.kper, q.relu,
+                  q.rs, p.splits > 1 ? static_cast<float *>(workspace) : nullptr, cnt, p.gx, p.gy,
+                  p.splits};
+}
+
+// ---- template dispatch: f is a generic lambda (integral constants: common.h IntC) -----------
+template <class F> void with_bool(bool b, F f) {
+  if (b) f(std::true_type());
+  else f(std::false_type());
+}
+// f(VEC): 2, 1 or 0 for a k-contiguous operand (KC), 0 alone for a row-contiguous one
+template <bool KC, class F> void with_vec(int vec, F f) {
+  if constexpr (KC) {
+    if (vec == 2) return f(IntC<2>());
+    if (vec == 1) return f(IntC<1>());
   }
-  if (skinny_ok(ak, bk, bias_rows, cols, M, rs)) {
-    const bool v2 = lda % 2 == 0 && ldb % 2 == 0 && ((uintptr_t)A & 7) == 0 && ((uintptr_t)B & 7) == 0;
-    const dim3 grid(N, cdiv(M, SK_MAXM));
-    if (v2)
-      hipLaunchKernelGGL(k_gemm_skinny<2>, grid, dim3(256), 0, s, A, lda, B, ldb, bias, Cadd, ldadd,
-                         C, ldc, M, N, K, relu);
-    else
-      hipLaunchKernelGGL(k_gemm_skinny<1>, grid, dim3(256), 0, s, A, lda, B, ldb, bias, Cadd, ldadd,
-                         C, ldc, M, N, K, relu);
+  f(IntC<0>());
+}
+// f(WM): waves along M of the two 32 x 32-wave-tile blocks, tile 2 (32 x 128) or tile 1 (64 x 64)
+template <class F> void with_wm(int tile, F f) {
+  if (tile == 2) f(IntC<1>());
+  else f(IntC<2>());
+}
+// f(WM, TM, TN, OP): the six fp32 tiles, the two bf16 ones
+template <class F> void with_tile_op(int tile, int op, F f) {
+  IntC<0> o;
+  IntC<1> i1;
+  IntC<2> i2;
+  if (op == 1) with_wm(tile, [&](auto wm) { f(wm, i1, i1, i1); });
+  else if (tile == 2) f(i1, i1, i1, o);
+  else if (tile == 3) f(i2, i2, i2, o);
+  else if (tile == 4) f(i2, i1, i2, o);
+  else if (tile == 5) f(i2, i2, i1, o);
+  else if (tile == 6) f(i1, i2, i2, o);
+  else f(i2, i1, i1, o);
+}
+
+void launch_tiles(const GemmProblem &q, const GemmPlan &p, const GemmArgs &ga, hipStream_t s) {
+  const dim3 grid(p.gx, p.gy, p.splits);
+  with_bool(q.ak, [&](auto ak) {
+    with_bool(q.bk, [&](auto bk) {
+      constexpr bool AK = decltype(ak)::value, BK = decltype(bk)::value;
+      with_vec<AK>(p.avec, [&](auto av) {
+        with_vec<BK>(p.bvec, [&](auto bv) {
+          with_tile_op(p.tile, p.op, [&](auto wm, auto tm, auto tn, auto op) {
+            hipLaunchKernelGGL((k_gemm<AK, BK, decltype(wm)::value, decltype(tm)::value,
+                                       decltype(tn)::value, decltype(av)::value,
+                                       decltype(bv)::value, decltype(op)::value>),
+                               grid, dim3(256), 0, s, ga);
+          });
+        });
+      });
+    });
+  });
+}
+
+// k_gemm_pair for (input gradient: A k-contiguous, B row-contiguous) + (weight gradient with
+// the row-sum column: both row-contiguous), over the tiles / vector width / precision
+void launch_pair(const GemmPlan &p1, const GemmArgs &g1, const GemmPlan &p2, const GemmArgs &g2,
+                 hipStream_t s) {
+  const dim3 grid(g1.gx * g1.gy * g1.gz + g2.gx * g2.gy * g2.gz);
+  with_bool(p1.op == 1, [&](auto op) {
+    with_wm(p1.tile, [&](auto wm1) {
+      with_vec<true>(p1.avec, [&](auto av1) {
+        with_wm(p2.tile, [&](auto wm2) {
+          constexpr int OP = decltype(op)::value ? 1 : 0;
+          hipLaunchKernelGGL(
+              (k_gemm_pair<GemmCfg<true, false, decltype(wm1)::value, 1, 1, decltype(av1)::value, 0, OP>,
+                           GemmCfg<false, false, decltype(wm2)::value, 1, 1, 0, 0, OP>>),
+              grid, dim3(256), 0, s, g1, g2);
+        });
+      });
+    });
+  });
+}
+
+int gemm_launch(const GemmProblem &q, const GemmPlan &p, void *workspace, hipStream_t s) {
+  if (p.route == GEMM_SKINNY) {
+    const dim3 grid(q.N, cdiv(q.M, SK_MAXM));
+    with_bool(p.skinny_v == 2, [&](auto v2) {
+      hipLaunchKernelGGL(k_gemm_skinny<(decltype(v2)::value ? 2 : 1)>, grid, dim3(256), 0, s, q.A,
+                         q.lda, q.B, q.ldb, q.bias, q.Cadd, q.ldadd, q.C, q.ldc, q.M, q.N, q.K, q.relu);
+    });
     return 0;
   }
-  const int Nx = rs ? N + 1 : N;  // logical columns including the ones column
-  GemmLaunch p = gemm_plan(M, Nx, K);
-  if (g_gemm_precision == 1 && p.tile != 1 && p.tile != 2) p.tile = 1;  // bf16: tiles 1 / 2 only
   if (p.splits > 1 && !workspace) {
     set_error("gemm: workspace of e2ep_gemm_workspace() bytes required");
     return E2EP_EINVAL;
   }
-  float *part = p.splits > 1 ? static_cast<float *>(workspace) : nullptr;
-  const GemmTile td = tile_dims(p.tile);
-  // in-launch split-K fold (e2ep_tune key 28 = 2): one arrival counter per output tile
-  unsigned int *cnt = (p.splits > 1 && g_tune[TUNE_SPLITK_FOLD] == 2)
-                          ? handoff_slots(cdiv(Nx, td.bn) * cdiv(M, td.bm), s) : nullptr;
-  dim3 grid(cdiv(Nx, td.bn), cdiv(M, td.bm), p.splits);
-  const int avec = vec_of(ak, lda, A), bvec = vec_of(bk, ldb, B);
-  const int br = bias_rows ? 1 : 0;
-  const GemmArgs ga{A, lda, a_bytes, B, ldb, b_bytes, bias, br, Cadd, ldadd, C, c_bytes, ldc,
-                    cols, M, N, K, p.kper, relu, rs, part, cnt, (int)grid.x, (int)grid.y,
-                    (int)grid.z};
-#define E2EP_GEMM_LAUNCH(AKV, BKV, WMV, TMV, TNV, AVV, BVV)                                     \
-  hipLaunchKernelGGL((k_gemm<AKV, BKV, WMV, TMV, TNV, AVV, BVV>), grid, dim3(256), 0, s, ga)
-#define E2EP_GEMM_T(AKV, BKV, AVV, BVV)                                     \
-  do {                                                                      \
-    if (g_gemm_precision == 1) { /* bf16: the automatic tiles */            \
-      if (p.tile == 2)                                                      \
-        hipLaunchKernelGGL((k_gemm<AKV, BKV, 1, 1, 1, AVV, BVV, 1>), grid, dim3(256), 0, s, ga); \
-      else                                                                  \
-        hipLaunchKernelGGL((k_gemm<AKV, BKV, 2, 1, 1, AVV, BVV, 1>), grid, dim3(256), 0, s, ga); \
-      break;                                                                \
-    }                                                                       \
-    switch (p.tile) {                                                       \
-      case 2: E2EP_GEMM_LAUNCH(AKV, BKV, 1, 1, 1, AVV, BVV); break;          \
-      case 3: E2EP_GEMM_LAUNCH(AKV, BKV, 2, 2, 2, AVV, BVV); break;          \
-      case 4: E2EP_GEMM_LAUNCH(AKV, BKV, 2, 1, 2, AVV, BVV); break;          \
-      case 5: E2EP_GEMM_LAUNCH(AKV, BKV, 2, 2, 1, AVV, BVV); break;          \
-      case 6: E2EP_GEMM_LAUNCH(AKV, BKV, 1, 2, 2, AVV, BVV); break;          \
-      default: E2EP_GEMM_LAUNCH(AKV, BKV, 2, 1, 1, AVV, BVV); break;         \
-    }                                                                       \
-  } while (0)
-  // vector widths along k of the k-contiguous operands (template: no run-time switch)
-#define E2EP_GEMM_BV(AKV, BKV, AVV)                 \
-  do {                                              \
-    if (bvec == 2) E2EP_GEMM_T(AKV, BKV, AVV, 2);    \
-    else if (bvec == 1) E2EP_GEMM_T(AKV, BKV, AVV, 1); \
-    else E2EP_GEMM_T(AKV, BKV, AVV, 0);              \
-  } while (0)
-  if (ak && bk) {
-    if (avec == 2) E2EP_GEMM_BV(true, true, 2);
-    else if (avec == 1) E2EP_GEMM_BV(true, true, 1);
-    else E2EP_GEMM_BV(true, true, 0);
-  } else if (ak) {
-    if (avec == 2) E2EP_GEMM_T(true, false, 2, 0);
-    else if (avec == 1) E2EP_GEMM_T(true, false, 1, 0);
-    else E2EP_GEMM_T(true, false, 0, 0);
-  } else if (bk) {
-    E2EP_GEMM_BV(false, true, 0);
-  } else {
-    E2EP_GEMM_T(false, false, 0, 0);
-  }
-#undef E2EP_GEMM_BV
-#undef E2EP_GEMM_T
-#undef E2EP_GEMM_LAUNCH
+  // a launch that wants the fold but gets no counters reduces in a second launch instead
+  unsigned int *cnt = p.route == GEMM_FOLD ? handoff_slots(p.gx * p.gy, s) : nullptr;
+  launch_tiles(q, p, gemm_args(q, p, workspace, cnt), s);
   if (p.splits > 1 && !cnt) {
-    const long long MN = (long long)M * Nx;
-    const bool v4 = !rs && MN % 4 == 0 && ldc == N && cols.hw == 0 && !bias_rows &&
-                    (!Cadd || ldadd == N) && ((uintptr_t)C & 15) == 0;
-    if (v4)
-      hipLaunchKernelGGL(k_gemm_reduce<4>, dim3(cdiv(MN / 4, 256)), dim3(256), 0, s,
-                         static_cast<const float *>(workspace), p.splits, M, N, bias, br, Cadd,
-                         ldadd, C, ldc, cols, relu, nullptr);
-    else
-      hipLaunchKernelGGL(k_gemm_reduce<1>, dim3(cdiv(MN, 256)), dim3(256), 0, s,
-                         static_cast<const float *>(workspace), p.splits, M, N, bias, br, Cadd,
-                         ldadd, C, ldc, cols, relu, rs);
+    const long long MN = (long long)q.M * p.nx;
+    with_bool(p.reduce_v == 4, [&](auto v4) {
+      constexpr int V = decltype(v4)::value ? 4 : 1;
+      hipLaunchKernelGGL(k_gemm_reduce<V>, dim3(cdiv(MN / V, 256)), dim3(256), 0, s,
+                         static_cast<const float *>(workspace), p.splits, q.M, q.N, q.bias,
+                         q.bias_rows ? 1 : 0, q.Cadd, q.ldadd, q.C, q.ldc, q.cols, q.relu, q.rs);
+    });
   }
   return 0;
 }
 
-// One problem of a k_gemm_pair launch: its plan, fold counters and arguments; false when the
-// pair kernel cannot take it (benchmark-forced tiles, or K splits without the in-launch fold).
-static bool gemm_prepare(const float *A, int lda, bool ak, long long a_bytes, const float *B,
-                         int ldb, bool bk, long long b_bytes, const float *Cadd, int ldadd,
-                         float *C, long long c_bytes, int ldc, int M, int N, int K,
-                         void *workspace, float *rs, hipStream_t s, GemmArgs &ga, int &wm,
-                         int &avec) {
-  const int Nx = rs ? N + 1 : N;
-  GemmLaunch p = gemm_plan(M, Nx, K);
-  if (g_gemm_precision == 1 && p.tile != 1 && p.tile != 2) p.tile = 1;
-  if (p.tile != 1 && p.tile != 2) return false;
-  if (p.splits > 1 && (!workspace || g_tune[TUNE_SPLITK_FOLD] != 2)) return false;
-  const GemmTile td = tile_dims(p.tile);
-  const int gx = cdiv(Nx, td.bn), gy = cdiv(M, td.bm);
-  unsigned int *cnt = p.splits > 1 ? handoff_slots(gx * gy, s) : nullptr;
-  if (p.splits > 1 && !cnt) return false;  // no counters: the two-launch path reduces
-  ga = GemmArgs{A, lda, a_bytes, B, ldb, b_bytes, nullptr, 0, Cadd, ldadd, C, c_bytes, ldc,
-                GemmCols{0, 0, 0}, M, N, K, p.kper, 0, rs,
-                p.splits > 1 ? static_cast<float *>(workspace) : nullptr, cnt, gx, gy, p.splits};
-  wm = p.tile == 2 ? 1 : 2;  // tile 1: 64 x 64 (2 x 2 waves); tile 2: 32 x 128 (1 x 4)
-  avec = vec_of(ak, lda, A);
-  (void)bk;
-  return true;
+// bytes from an operand's base to the end of its last row: `rows` rows of `cols` floats, ld apart
+long long extent_bytes(int rows, int ld, int cols) { return 4LL * ((long long)(rows - 1) * ld + cols); }
+
+// a plain-matrix problem's operand extents from its dimensions and leading dimensions
+void set_extents(GemmProblem &q) {
+  q.a_bytes = q.ak ? extent_bytes(q.M, q.lda, q.K) : extent_bytes(q.K, q.lda, q.M);
+  q.b_bytes = q.bk ? extent_bytes(q.N, q.ldb, q.K) : extent_bytes(q.K, q.ldb, q.N);
+  q.c_bytes = extent_bytes(q.M, q.ldc, q.N);
 }
 
-// k_gemm_pair for (input gradient: A k-contiguous, B row-contiguous) + (weight gradient with
-// the row-sum column: both row-contiguous), dispatched over the tiles / vector width / precision
-template <int OP, int WM1, int AV1, int WM2>
-static void pair4(dim3 grid, hipStream_t s, const GemmArgs &g1, const GemmArgs &g2) {
-  hipLaunchKernelGGL((k_gemm_pair<GemmCfg<true, false, WM1, 1, 1, AV1, 0, OP>,
-                                  GemmCfg<false, false, WM2, 1, 1, 0, 0, OP>>),
-                     grid, dim3(256), 0, s, g1, g2);
+// An entry point's check of one (plain-matrix) problem: leading dimensions, the workspace its
+// plan needs, 32-bit byte offsets.
+int gemm_check(const char *who, const GemmProblem &q, const GemmPlan &p, const void *ws, size_t ws_bytes) {
+  E2EP_REQUIRE(q.lda >= (q.ak ? q.K : q.M) && q.ldb >= (q.bk ? q.K : q.N) && q.ldc >= q.N &&
+                   (!q.Cadd || q.ldadd >= q.N),
+               E2EP_EINVAL, "%s: leading dimension too small", who);
+  E2EP_REQUIRE(!p.ws_bytes || (ws && ws_bytes >= p.ws_bytes), E2EP_EINVAL,
+               "%s: workspace %zu bytes < %zu the launch plan of the %d x %d x %d product needs (query "
+               "e2ep_gemm_workspace / e2ep_gemm_rowsum_workspace after setting precision / tunables)",
+               who, ws_bytes, p.ws_bytes, q.M, q.N, q.K);
+  const long long lim = 0x7fffffffLL;
+  E2EP_REQUIRE(q.a_bytes < lim && q.b_bytes < lim && q.c_bytes < lim &&
+                   (!q.Cadd || extent_bytes(q.M, q.ldadd, q.N) < lim) &&
+                   (!q.rs || 4LL * q.M * (q.N + 1) * 8 < lim),
+               E2EP_ERANGE, "%s: operand larger than 2 GB", who);
+  return 0;
 }
-template <int OP, int WM1, int AV1>
-static void pair3(int wm2, dim3 grid, hipStream_t s, const GemmArgs &g1, const GemmArgs &g2) {
-  if (wm2 == 2) pair4<OP, WM1, AV1, 2>(grid, s, g1, g2);
-  else pair4<OP, WM1, AV1, 1>(grid, s, g1, g2);
+
+}  // namespace
+
+int gemm_run(const GemmProblem &q, void *workspace, hipStream_t s) {
+  if (q.rs && (q.ak || q.bk || q.cols.hw)) {
+    set_error("gemm: the row sum of A needs a k-major A, a row-contiguous B, unbatched C");
+    return E2EP_EINVAL;
+  }
+  return gemm_launch(q, gemm_plan(q), workspace, s);
 }
-template <int OP, int WM1>
-static void pair2(int av1, int wm2, dim3 grid, hipStream_t s, const GemmArgs &g1, const GemmArgs &g2) {
-  if (av1 == 2) pair3<OP, WM1, 2>(wm2, grid, s, g1, g2);
-  else if (av1 == 1) pair3<OP, WM1, 1>(wm2, grid, s, g1, g2);
-  else pair3<OP, WM1, 0>(wm2, grid, s, g1, g2);
-}
-template <int OP>
-static void pair1(int wm1, int av1, int wm2, dim3 grid, hipStream_t s, const GemmArgs &g1,
-                  const GemmArgs &g2) {
-  if (wm1 == 2) pair2<OP, 2>(av1, wm2, grid, s, g1, g2);
-  else pair2<OP, 1>(av1, wm2, grid, s, g1, g2);
+
+size_t gemm_ws(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  GemmProblem q{};
+  q.M = M, q.N = N, q.K = K;
+  return gemm_plan(q).ws_bytes;
 }
 
 }  // namespace e2ep
@@ -755,45 +786,30 @@ int e2ep_linear_bwd(const float *dy, int ldy, const float *x, int ldx, const flo
                     size_t ws_dw_bytes, void *stream) {
   E2EP_REQUIRE(dy && x && w && dx && dw && db && M > 0 && N > 0 && K > 0, E2EP_EINVAL,
                "e2ep_linear_bwd: bad arguments M=%d N=%d K=%d", M, N, K);
-  E2EP_REQUIRE(ldy >= N && ldx >= K && ldw >= K && lddx >= K && lddw >= K &&
-                   (!gskip || ldskip >= K),
-               E2EP_EINVAL, "e2ep_linear_bwd: leading dimension too small");
-  const size_t need_dx = gemm_ws(M, K, N), need_dw = gemm_ws(N, K + 1, M);
-  E2EP_REQUIRE((!need_dx || (ws_dx && ws_dx_bytes >= need_dx)) &&
-                   (!need_dw || (ws_dw && ws_dw_bytes >= need_dw)),
-               E2EP_EINVAL, "e2ep_linear_bwd: workspaces %zu / %zu bytes < %zu / %zu "
-               "(e2ep_gemm_workspace(M, K, N) / e2ep_gemm_rowsum_workspace(N, K, M))",
-               ws_dx_bytes, ws_dw_bytes, need_dx, need_dw);
-  const long long y_bytes = 4LL * ((long long)(M - 1) * ldy + N);
-  const long long x_bytes = 4LL * ((long long)(M - 1) * ldx + K);
-  const long long w_bytes = 4LL * ((long long)(N - 1) * ldw + K);
-  const long long dx_bytes = 4LL * ((long long)(M - 1) * lddx + K);
-  const long long dw_bytes = 4LL * ((long long)(N - 1) * lddw + K);
-  E2EP_REQUIRE(y_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL && w_bytes < 0x7fffffffLL &&
-                   dx_bytes < 0x7fffffffLL && dw_bytes < 0x7fffffffLL &&
-                   4LL * N * (K + 1) * 8 < 0x7fffffffLL,
-               E2EP_ERANGE, "e2ep_linear_bwd: operand larger than 2 GB");
-  hipStream_t s = as_stream(stream);
   // dX[M][K] = dY[M][N] W[N][K] (+ gskip);  dW[N][K] = dY^T X with db[N] = row sums of dY^T
-  GemmArgs g1, g2;
-  int wm1, av1, wm2, av2;
-  if (g_force_tile == 0 &&
-      gemm_prepare(dy, ldy, true, y_bytes, w, ldw, false, w_bytes, gskip, ldskip, dx, dx_bytes,
-                   lddx, M, K, N, ws_dx, nullptr, s, g1, wm1, av1) &&
-      gemm_prepare(dy, ldy, false, y_bytes, x, ldx, false, x_bytes, nullptr, 0, dw, dw_bytes,
-                   lddw, N, K, M, ws_dw, db, s, g2, wm2, av2)) {
-    const dim3 grid(g1.gx * g1.gy * g1.gz + g2.gx * g2.gy * g2.gz);
-    if (g_gemm_precision == 1) pair1<1>(wm1, av1, wm2, grid, s, g1, g2);
-    else pair1<0>(wm1, av1, wm2, grid, s, g1, g2);
-    return launch_status("e2ep_linear_bwd");
+  GemmProblem qx{}, qw{};
+  qx.A = dy, qx.lda = ldy, qx.ak = true, qx.B = w, qx.ldb = ldw, qx.C = dx, qx.ldc = lddx;
+  qx.Cadd = gskip, qx.ldadd = ldskip;
+  qx.M = M, qx.N = K, qx.K = N;
+  qw.A = dy, qw.lda = ldy, qw.B = x, qw.ldb = ldx, qw.C = dw, qw.ldc = lddw, qw.rs = db;
+  qw.M = N, qw.N = K, qw.K = M;
+  set_extents(qx), set_extents(qw);
+  const GemmPlan px = gemm_plan(qx), pw = gemm_plan(qw);
+  if (int rc = gemm_check("e2ep_linear_bwd", qx, px, ws_dx, ws_dx_bytes)) return rc;
+  if (int rc = gemm_check("e2ep_linear_bwd", qw, pw, ws_dw, ws_dw_bytes)) return rc;
+  hipStream_t s = as_stream(stream);
+  if (px.pairable && pw.pairable) {
+    // counters only now that both halves pair; a split half that gets none: two launches below
+    unsigned int *cx = nullptr, *cw = nullptr;
+    if ((px.splits == 1 || (cx = handoff_slots(px.gx * px.gy, s))) &&
+        (pw.splits == 1 || (cw = handoff_slots(pw.gx * pw.gy, s)))) {
+      launch_pair(px, gemm_args(qx, px, ws_dx, cx), pw, gemm_args(qw, pw, ws_dw, cw), s);
+      return launch_status("e2ep_linear_bwd");
+    }
   }
   // fallback (benchmark-forced tiles, folds off): the two launches in order on one stream
-  int rc = gemm_run(dy, ldy, true, y_bytes, w, ldw, false, w_bytes, nullptr, false, gskip, ldskip,
-                    dx, dx_bytes, lddx, GemmCols{0, 0, 0}, M, K, N, 0, ws_dx, s, nullptr);
-  if (rc) return rc;
-  rc = gemm_run(dy, ldy, false, y_bytes, x, ldx, false, x_bytes, nullptr, false, nullptr, 0, dw,
-                dw_bytes, lddw, GemmCols{0, 0, 0}, N, K, M, 0, ws_dw, s, db);
-  if (rc) return rc;
+  if (int rc = gemm_launch(qx, px, ws_dx, s)) return rc;
+  if (int rc = gemm_launch(qw, pw, ws_dw, s)) return rc;
   return launch_status("e2ep_linear_bwd");
 }
 
@@ -805,8 +821,6 @@ int e2ep_gemm_force(int tile, int splits, int unused) {
   g_force_splits = splits;
   return 0;
 }
-
-size_t e2ep_gemm_workspace(int M, int N, int K) { return gemm_ws(M, N, K); }
 
 int e2ep_gemm_split_min(int ksteps) {
   const int prev = g_split_min_small;
@@ -825,6 +839,8 @@ int e2ep_gemm_skinny(int max_rows) {
   if (max_rows >= 0) g_skinny_rows = std::min(max_rows, SK_ROWS);
   return prev;
 }
+
+size_t e2ep_gemm_workspace(int M, int N, int K) { return gemm_ws(M, N, K); }
 size_t e2ep_gemm_rowsum_workspace(int M, int N, int K) { return gemm_ws(M, N + 1, K); }
 
 int e2ep_gemm(const float *A, int lda, int a_kcontig, const float *B, int ldb, int b_kcontig,
@@ -832,23 +848,14 @@ int e2ep_gemm(const float *A, int lda, int a_kcontig, const float *B, int ldb, i
               int K, int relu, void *workspace, size_t workspace_bytes, void *stream) {
   E2EP_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, E2EP_EINVAL,
                "e2ep_gemm: bad arguments M=%d N=%d K=%d", M, N, K);
-  E2EP_REQUIRE(!gemm_ws(M, N, K) || (workspace && workspace_bytes >= gemm_ws(M, N, K)),
-               E2EP_EINVAL, "e2ep_gemm: workspace %zu bytes < %zu the launch plan needs (query "
-               "e2ep_gemm_workspace after setting precision / tunables)", workspace_bytes,
-               gemm_ws(M, N, K));
-  E2EP_REQUIRE(lda >= (a_kcontig ? K : M) && ldb >= (b_kcontig ? K : N) && ldc >= N &&
-                   (!Cadd || ldadd >= N),
-               E2EP_EINVAL, "e2ep_gemm: leading dimension too small");
-  const long long a_bytes = 4LL * (a_kcontig ? (long long)(M - 1) * lda + K : (long long)(K - 1) * lda + M);
-  const long long b_bytes = 4LL * (b_kcontig ? (long long)(N - 1) * ldb + K : (long long)(K - 1) * ldb + N);
-  const long long c_bytes = 4LL * ((long long)(M - 1) * ldc + N);
-  E2EP_REQUIRE(a_bytes < 0x7fffffffLL && b_bytes < 0x7fffffffLL && c_bytes < 0x7fffffffLL &&
-                   (!Cadd || 4LL * ((long long)(M - 1) * ldadd + N) < 0x7fffffffLL),
-               E2EP_ERANGE, "e2ep_gemm: operand larger than 2 GB");
-  const int rc = gemm_run(A, lda, a_kcontig, a_bytes, B, ldb, b_kcontig, b_bytes, bias, false,
-                          Cadd, ldadd, C, c_bytes, ldc, GemmCols{0, 0, 0}, M, N, K, relu,
-                          workspace, as_stream(stream), nullptr);
-  if (rc) return rc;
+  GemmProblem q{};
+  q.A = A, q.lda = lda, q.ak = a_kcontig, q.B = B, q.ldb = ldb, q.bk = b_kcontig, q.C = C, q.ldc = ldc;
+  q.bias = bias, q.Cadd = Cadd, q.ldadd = ldadd, q.relu = relu;
+  q.M = M, q.N = N, q.K = K;
+  set_extents(q);
+  const GemmPlan p = gemm_plan(q);
+  if (int rc = gemm_check("e2ep_gemm", q, p, workspace, workspace_bytes)) return rc;
+  if (int rc = gemm_launch(q, p, workspace, as_stream(stream))) return rc;
   return launch_status("e2ep_gemm");
 }
 
@@ -857,21 +864,13 @@ int e2ep_gemm_rowsum(const float *A, int lda, const float *B, int ldb, float *C,
                      size_t workspace_bytes, void *stream) {
   E2EP_REQUIRE(A && B && C && rowsum && M > 0 && N > 0 && K > 0, E2EP_EINVAL,
                "e2ep_gemm_rowsum: bad arguments M=%d N=%d K=%d", M, N, K);
-  E2EP_REQUIRE(!gemm_ws(M, N + 1, K) || (workspace && workspace_bytes >= gemm_ws(M, N + 1, K)),
-               E2EP_EINVAL, "e2ep_gemm_rowsum: workspace %zu bytes < %zu the launch plan needs",
-               workspace_bytes, gemm_ws(M, N + 1, K));
-  E2EP_REQUIRE(lda >= M && ldb >= N && ldc >= N, E2EP_EINVAL,
-               "e2ep_gemm_rowsum: leading dimension too small");
-  const long long a_bytes = 4LL * ((long long)(K - 1) * lda + M);
-  const long long b_bytes = 4LL * ((long long)(K - 1) * ldb + N);
-  const long long c_bytes = 4LL * ((long long)(M - 1) * ldc + N);
-  E2EP_REQUIRE(a_bytes < 0x7fffffffLL && b_bytes < 0x7fffffffLL && c_bytes < 0x7fffffffLL &&
-                   4LL * M * (N + 1) * 8 < 0x7fffffffLL,
-               E2EP_ERANGE, "e2ep_gemm_rowsum: operand larger than 2 GB");
-  const int rc = gemm_run(A, lda, false, a_bytes, B, ldb, false, b_bytes, nullptr, false, nullptr,
-                          0, C, c_bytes, ldc, GemmCols{0, 0, 0}, M, N, K, 0, workspace,
-                          as_stream(stream), rowsum);
-  if (rc) return rc;
+  GemmProblem q{};
+  q.A = A, q.lda = lda, q.B = B, q.ldb = ldb, q.C = C, q.ldc = ldc, q.rs = rowsum;
+  q.M = M, q.N = N, q.K = K;
+  set_extents(q);
+  const GemmPlan p = gemm_plan(q);
+  if (int rc = gemm_check("e2ep_gemm_rowsum", q, p, workspace, workspace_bytes)) return rc;
+  if (int rc = gemm_launch(q, p, workspace, as_stream(stream))) return rc;
   return launch_status("e2ep_gemm_rowsum");
 }
 

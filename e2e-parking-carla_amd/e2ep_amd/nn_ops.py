@@ -1228,17 +1228,20 @@ def _linear_bwd(g2, x2, weight, want_x, want_w, want_b, gskip=None, dw=None, db=
     M, K = x2.shape
     N = weight.shape[0]
     dx = None
+    lib = _lib.load()
+    # every buffer allocated here, on the current stream, before any fork (conv._Fork)
+    if want_w and dw is None:
+        dw = torch.empty(N, K, dtype=torch.float32, device=g2.device)
+    if want_b and db is None:
+        db = torch.empty(N, dtype=torch.float32, device=g2.device)
+    if want_w:  # dW's split-K workspace: with the row-sum column when db rides in its launch
+        wsw = _ws(lib.e2ep_gemm_rowsum_workspace(N, K, M) if want_b
+                  else lib.e2ep_gemm_workspace(N, K, M), g2.device)
     if want_x and want_w and want_b and _PAIR[0]:
         # all three in one launch (e2ep_linear_bwd: k_gemm_pair), no side-stream fork / join
-        if dw is None:
-            dw = torch.empty(N, K, dtype=torch.float32, device=g2.device)
-        if db is None:
-            db = torch.empty(N, dtype=torch.float32, device=g2.device)
         cadd = _skip_rows(gskip, M, K)
         dx = torch.empty(M, K, dtype=torch.float32, device=g2.device)
-        lib = _lib.load()
         wsx = _ws(lib.e2ep_gemm_workspace(M, K, N), g2.device)
-        wsw = _ws(lib.e2ep_gemm_rowsum_workspace(N, K, M), g2.device)
         w2 = weight if weight.stride(1) == 1 else weight.contiguous()
         with timing.region(timing.name("gemm", (M, N, K), "linear_bwd_pair"), 4.0 * M * N * K):
             _lib.call("e2ep_linear_bwd", _lib.ptr(g2), g2.stride(0), _lib.ptr(x2), x2.stride(0),
@@ -1248,18 +1251,9 @@ def _linear_bwd(g2, x2, weight, want_x, want_w, want_b, gskip=None, dw=None, db=
                       _lib.nbytes(wsx), _lib.ptr(wsw), _lib.nbytes(wsw), _lib.stream())
         return dx, dw, db
     # weight / bias gradients on the side stream, concurrent with the input gradient
-    # (conv._Fork: every buffer allocated here, on the current stream, before the fork)
     fork = None
     if want_w or want_b:
-        if want_w:
-            if dw is None:
-                dw = torch.empty(N, K, dtype=torch.float32, device=g2.device)
-            wsw = _ws(_lib.load().e2ep_gemm_rowsum_workspace(N, K, M) if want_b
-                      else _lib.load().e2ep_gemm_workspace(N, K, M), g2.device)
-        if want_b:
-            if db is None:
-                db = torch.empty(N, dtype=torch.float32, device=g2.device)
-            wsb = None if want_w else _ws(_lib.load().e2ep_col_sum_workspace(M, N), g2.device)
+        wsb = None if want_w else _ws(lib.e2ep_col_sum_workspace(M, N), g2.device)
         fork = conv._Fork(g2.device, on=want_x, work_us=conv.est_us(2.0 * N * K * M))
         with fork:
             if want_w and want_b:  # dW and db in one launch

@@ -90,9 +90,34 @@ def _ref_core(q, k, v, keep, p, causal, kpm):
 @pytest.mark.parametrize("Sq,Sk,causal", [(256, 256, False), (14, 14, True), (14, 256, False),
                                                 (16, 16, True), (17, 9, False)])
 def test_attention_dropout_matches_masked_reference(Sq, Sk, causal):
+    _dropout_case(Sq, Sk, causal)
+
+
+# (head dim, S, e2ep_tune key 20, split backward): the vector-kernel instantiations no test
+# above launches.  k_attn_fwd / k_attn_bwd_q / k_attn_bwd_kv<DHP, LANES>: <44, 2> (dh 43, key 20 =
+# 2), <64, 1> (dh 64 at 17 > 16 tokens), <64, 2>, <64, 4> (14 tokens); k_attn_bwd_d<64> (the
+# split backward's D pass, which also runs dq and dk / dv as parts 2 and 3).
+@pytest.mark.parametrize("dh,S,lanes,split", [(43, 17, 2, False), (64, 17, 1, False), (64, 17, 2, False),
+                                              (64, 14, 1, False), (64, 17, 1, True)])
+def test_attention_vector_kernel_variants(dh, S, lanes, split):
+    from e2ep_amd import _lib, attention, conv
+    old = _lib.call_raw("e2ep_tune", 20, lanes)
+    split0, attention._SPLIT_BWD = attention._SPLIT_BWD, split
+    prev, prev_us = conv.set_wgrad_overlap(split), conv.set_fork_min_us(0)
+    try:
+        _dropout_case(S, S, False, B=2, dh=dh)
+    finally:
+        conv.set_wgrad_overlap(prev)
+        conv.set_fork_min_us(prev_us)
+        attention._SPLIT_BWD = split0
+        _lib.call_raw("e2ep_tune", 20, old)
+    assert _lib.call_raw("e2ep_tune", 20, 0) == old
+
+
+def _dropout_case(Sq, Sk, causal, B=4, dh=43):
     from e2ep_amd import _lib, attention
     g = torch.Generator().manual_seed(11)
-    B, dh, p = 4, 43, 0.1
+    p = 0.1
     Ed = H * dh
     qb = torch.randn(Sq, B, Ed, generator=g)
     kvb = torch.randn(Sk, B, 2 * Ed, generator=g)

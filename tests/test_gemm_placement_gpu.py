@@ -34,7 +34,9 @@ Where each instantiation is reached (test ids):
         k_gemm_reduce<1> writing rowsum       test_rowsum[t{1,2}-reduce]
     k_gemm_pair<..., AV1>, unsplit            test_linear_bwd[*-plan-*]
     k_gemm_pair with both problems split      test_linear_bwd[*-split-*]
-    k_gemm_reduce<4> (dense aligned C)        the dense controls of every `reduce` setting"""
+    k_gemm_reduce<4> (dense aligned C)        the dense controls of every `reduce` setting
+    every other k_gemm / k_gemm_pair built    test_remaining_instantiations, test_linear_bwd_
+                                              remaining_instantiations (33 x 70 x 77, unsplit)"""
 import contextlib
 
 import pytest
@@ -247,6 +249,41 @@ def test_large_tiles_mixed_placement(tile):
     assert (_vec_class(A), _vec_class(B)) == (1, 0)
 
 
+def _terminals():
+    """(ak, bk, AVEC, BVEC, tile, bf16) of the k_gemm instantiations the tests above and
+    test_gemm_gpu.py leave out (read off a kernel trace of both files): the large tiles at every
+    vector-width pair but (0, 0) and (1, 0) for the forward layout, and at a vector width at all
+    for the other two layouts; bf16 operands for the layouts with one k-contiguous operand."""
+    big = (3, 4, 5, 6)
+    out = [(True, True, a, b, t, False) for a in (0, 1, 2) for b in (0, 1, 2) for t in big
+           if (a, b) not in ((0, 0), (1, 0))]
+    out += [(True, False, 1, 0, t, False) for t in (3, 5, 6)]
+    out += [(True, False, 2, 0, t, False) for t in big]
+    out += [(True, False, 0, 0, 1, True), (True, False, 1, 0, 2, True)]
+    out += [(False, True, 0, b, t, False) for b in (1, 2) for t in big]
+    out += [(False, True, 0, b, t, True) for b in (0, 1, 2) for t in (1, 2)]
+    return out
+
+
+SMALL = 33, 70  # two 32-row tiles; a ragged last tile at every block width
+VEC_PLACE = {2: "v2", 1: "v1p", 0: "v0p"}
+
+
+@pytest.mark.parametrize("ak,bk,avec,bvec,tile,bf16", _terminals(),
+                         ids=[f"{'FT'[a]}{'FT'[b]}-a{av}-b{bv}-t{t}-{'bf16' if h else 'fp32'}"
+                              for a, b, av, bv, t, h in _terminals()])
+def test_remaining_instantiations(ak, bk, avec, bvec, tile, bf16):
+    """One small unsplit product per k_gemm<AK, BKC, tile, AVEC, BVEC, OP> no other test launches."""
+    m, n = SMALL
+    prob = _Problem(m, n, 77, ak, bk, bf16=bf16)
+    pa = KPLACE[VEC_PLACE[avec]] if ak else (m + ROWC[0], ROWC[1])
+    pb = KPLACE[VEC_PLACE[bvec]] if bk else (n + ROWC[0], ROWC[1])
+    with _settings(tile, 1, None, bf16):
+        setting = (tile, "nosplit", bf16)
+        A, B = prob.run(setting, pa, pb, False, n + 3, f"tile {tile} bf16 {bf16}")
+    assert (_vec_class(A) if ak else 0, _vec_class(B) if bk else 0) == (avec, bvec)
+
+
 # ------------------------------------------------------------------------------------------
 # k_gemm_skinny
 # ------------------------------------------------------------------------------------------
@@ -352,10 +389,10 @@ LB = 70, 77, 50  # rows M, out features N (dy's row length), in features K
 DY_PLACE = ["v2", "v1p", "v1l", "v0p", "v0l"]  # (v0d is the minimal ldy)
 
 
-def _linear_bwd(dy, x, w, gs, dx, dw, db):
+def _linear_bwd(dy, x, w, gs, dx, dw, db, dims=LB):
     L = _lib()
     lib = L.load()
-    m, n, k = LB
+    m, n, k = dims
     wsx = torch.empty(max(16, lib.e2ep_gemm_workspace(m, k, n)), dtype=torch.uint8, device=DEV)
     wsw = torch.empty(max(16, lib.e2ep_gemm_rowsum_workspace(n, k, m)), dtype=torch.uint8, device=DEV)
     L.call("e2ep_linear_bwd", L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), L.ptr(w), w.stride(0),
@@ -407,6 +444,42 @@ def test_linear_bwd(prec, plan, skip, p):
                 _check(dw, want_dw, dwd, what + " dw")
                 _check(db, want_db, dbd, what + " db")
             gd.check()
+
+
+# (rows M, out features N, AV1, precision): 20 rows or features put that half on the 32 x 128
+# tile (WM = 1: 20 mod 64 is in 1..32), 40 on the 64 x 64 tile (WM = 2); dy's row length is N.
+# The k_gemm_pair<WM1, AV1, OP, WM2> that test_linear_bwd and test_gemm_gpu.py leave out (read
+# off a kernel trace).
+PAIR_REST = [(20, 40, 0, "fp32"), (20, 40, 0, "bf16"), (20, 40, 1, "bf16"), (20, 40, 2, "bf16"),
+             (40, 20, 0, "fp32"), (40, 40, 0, "fp32"), (40, 20, 0, "bf16"), (40, 40, 0, "bf16"),
+             (40, 40, 1, "bf16"), (40, 20, 2, "bf16")]
+# dy's (ld - N, off) per vector width
+DY_VEC = {40: {2: (0, 0), 1: (0, 2), 0: (1, 0)}, 20: {2: (0, 0), 1: (2, 0), 0: (1, 0)}}
+
+
+@pytest.mark.parametrize("m,n,av1,prec", PAIR_REST,
+                         ids=[f"M{m}-N{n}-av{a}-{p}" for m, n, a, p in PAIR_REST])
+def test_linear_bwd_remaining_instantiations(m, n, av1, prec):
+    """One small unsplit e2ep_linear_bwd per k_gemm_pair instantiation no other test launches."""
+    k = 50
+    g = torch.Generator().manual_seed(m + 2 * n)
+    dy, x = torch.randn(m, n, generator=g), torch.randn(m, k, generator=g)
+    w = torch.randn(n, k, generator=g) / k ** 0.5
+    r = (lambda t: t.bfloat16().double()) if prec == "bf16" else (lambda t: t.double())
+    dld, offy = DY_VEC[n][av1]
+    with _settings(0, 0, None, prec == "bf16"):
+        dxd, dwd, dbd = (torch.full(s, float("nan"), device=DEV) for s in ((m, k), (n, k), (n,)))
+        need = _linear_bwd(dy.to(DEV), x.to(DEV), w.to(DEV), None, dxd, dwd, dbd, (m, n, k))
+        assert need == (0, 0)  # neither problem splits
+        dyp = P.placed(dy, n + dld, offy, device=DEV)
+        assert _vec_class(dyp) == av1
+        dx, dw, db = P.out((m, k), k + 3, 1, device=DEV), P.out((n, k), k + 5, 3, device=DEV), P.out((n,), None, 2, device=DEV)
+        _linear_bwd(dyp, P.placed(x, k + 1, 1, device=DEV), P.placed(w, k + 7, 3, device=DEV), None,
+                    dx, dw, db, (m, n, k))
+    what = f"linear_bwd {prec} M {m} N {n} av1 {av1}"
+    _check(dx, r(dy) @ r(w), dxd, what + " dx")
+    _check(dw, r(dy).t() @ r(x), dwd, what + " dw")
+    _check(db, r(dy).sum(0), dbd, what + " db")
 
 
 # ------------------------------------------------------------------------------------------
