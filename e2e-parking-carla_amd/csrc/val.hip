@@ -1,0 +1,368 @@
+// The validation half of an epoch on the device (fp32 logits in, device scalars and integer
+// counts out), replacing the reference's PyTorch op chains:
+//   control metrics  loss/control_loss.py:45-75 (ControlValLoss.forward): three slices, three
+//       softmaxes, two argmaxes, the Python detokenize loop behind a synchronising .tolist(),
+//       two SmoothL1Loss, two partial sums, stack, .T and CrossEntropyLoss;
+//   val_loss         trainer/pl_trainer.py:85-114 (validation_step): sum(d.values()) of the
+//       four losses, logged per batch;
+//   segmentation IoU the confusion matrix of the BEV head's per-pixel argmax (the class the
+//       agent steers by: agent.hip), which the reference never reports.
+// Kernels:
+//   k_ctrl_val_rows   one wave per used row 3f + k of each sample (rows T-2 and T-1 are not
+//       used).  k = 0 / 1: the argmax token in torch.argmax's order (argmax.h), detokenised,
+//       SmoothL1 (beta 1) against gt_acc / gt_steer.  k = 2: the fp32 softmax, its mass below
+//       and from `split`, and the 2-way cross entropy of that pair used as logits.
+//   k_ctrl_val_final  one workgroup: the per-row values summed by index, the two means and
+//       the reverse mean over its non-ignored rows (NaN when there is none, as torch).
+//   k_seg_conf_partials  grid (pixel chunks, images): per-pixel argmax, one ballot + popcount
+//       per confusion cell, int32 counts per workgroup.
+//   k_seg_conf_final  one workgroup: the partials summed by index in int64.
+//   k_val_accumulate  one wave: val_loss = ((acc_steer + reverse) + seg) + depth in fp32, the
+//       five values added to float64 running sums, the confusion matrix to an int64 running
+//       matrix, the batch counter incremented; one packed buffer.
+// One documented difference from the reference: it takes the argmax of the fp32 softmax, this
+// file the argmax of the logits.  The two agree whenever the row's two largest logits are
+// exactly equal (both pick the first index) and whenever they are far enough apart that their
+// fp32 probabilities differ; between the two, distinct logits can round to equal
+// probabilities, where the reference then picks the lower index and this kernel the larger
+// logit.
+// No atomics, nothing passed between workgroups inside a launch, every reduction in a fixed
+// order, no host read: every launch is capturable.  A label value never forms an address: it
+// is compared, or selects between two registers.
+#include "argmax.h"
+#include "common.h"
+
+namespace e2ep {
+
+constexpr int VAL_THREADS = 256;
+constexpr int VAL_WAVES = VAL_THREADS / 64;
+constexpr int CONF_MAX_C = 8;
+constexpr int CONF_CELLS = CONF_MAX_C * CONF_MAX_C;  // cell slots per workgroup (C * C used)
+constexpr int CONF_CHUNK = 2048;                     // pixels per workgroup, a multiple of 4
+
+__device__ __forceinline__ float val_block_sum(float v, float *red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.f;
+  for (int i = 0; i < VAL_WAVES; ++i) t += red[i];
+  return t;
+}
+
+// torch SmoothL1Loss, beta = 1
+__device__ __forceinline__ float smooth_l1(float x, float y) {
+  const float d = fabsf(x - y);
+  return d < 1.f ? 0.5f * d * d : d - 0.5f;
+}
+
+// row_vals: [acc | steer | reverse | reverse valid], B * F floats each
+__global__ void __launch_bounds__(VAL_THREADS)
+    k_ctrl_val_rows(const float *__restrict__ x, const float *__restrict__ gt_acc,
+                    const float *__restrict__ gt_steer, const long long *__restrict__ gt_rev, int B,
+                    int T, int V, int F, int valid_token, int split, int pad,
+                    float *__restrict__ row_vals) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * VAL_WAVES + (threadIdx.x >> 6);
+  const long long n = (long long)B * F;
+  if (r >= n * 3) return;
+  const int b = (int)(r / (3 * F)), j = (int)(r - (long long)b * 3 * F), f = j / 3, k = j - f * 3;
+  const float *xr = x + ((long long)b * T + j) * V;
+  const long long i = (long long)b * F + f;
+  if (k < 2) {
+    float best = -INFINITY;
+    int bi = 0x7fffffff;  // ranks below every real candidate of equal value
+    for (int v = lane; v < V; v += 64) {
+      const float a = xr[v];
+      if (argmax_beats(a, v, best, bi)) best = a, bi = v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (argmax_beats(ob, oi, best, bi)) best = ob, bi = oi;
+    }
+    if (lane == 0) {
+      float pred;
+      if (k == 0) {
+        // detokenize_acc on a Python int: float64, rounded by np.float32 afterwards
+        const double half = (double)valid_token / 2.0, a = (double)bi / half - 1.0;
+        pred = (float)((double)bi > half ? a : -a);
+        row_vals[i] = smooth_l1(pred, gt_acc[i]);
+      } else {
+        // detokenize_steer on an int64 tensor and a Python float: fp32 arithmetic
+        pred = (float)bi / (float)((double)valid_token / 2.0) - 1.f;
+        row_vals[n + i] = smooth_l1(pred, gt_steer[i]);
+      }
+    }
+    return;
+  }
+  float m = -INFINITY;
+  for (int v = lane; v < V; v += 64) m = fmaxf(m, xr[v]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  float s = 0.f;
+  for (int v = lane; v < V; v += 64) s += expf(xr[v] - m);
+  s = wave_sum(s);
+  float no = 0.f, yes = 0.f;
+  for (int v = lane; v < V; v += 64) {
+    const float p = expf(xr[v] - m) / s;
+    no += v < split ? p : 0.f;
+    yes += v < split ? 0.f : p;
+  }
+  no = wave_sum(no);
+  yes = wave_sum(yes);
+  if (lane == 0) {
+    const long long t = gt_rev[i];
+    const bool ok = t != pad && (t == 0 || t == 1);
+    // cross entropy of the logits (no, yes): logsumexp - the target's
+    const float mx = fmaxf(no, yes);
+    const float lse = mx + logf(expf(no - mx) + expf(yes - mx));
+    row_vals[2 * n + i] = ok ? lse - (t == 0 ? no : yes) : 0.f;
+    row_vals[3 * n + i] = ok ? 1.f : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(VAL_THREADS)
+    k_ctrl_val_final(const float *__restrict__ row_vals, int n, float *__restrict__ out) {
+  __shared__ float red[VAL_WAVES];
+  float a = 0.f, s = 0.f, r = 0.f, c = 0.f;
+  for (int i = threadIdx.x; i < n; i += VAL_THREADS) {
+    a += row_vals[i];
+    s += row_vals[(long long)n + i];
+    r += row_vals[2LL * n + i];
+    c += row_vals[3LL * n + i];
+  }
+  const float sa = val_block_sum(a, red), ss = val_block_sum(s, red);
+  const float sr = val_block_sum(r, red), sc = val_block_sum(c, red);
+  if (threadIdx.x == 0) {
+    out[0] = sa / (float)n + ss / (float)n;
+    out[1] = sc > 0.f ? sr / sc : NAN;  // torch: mean over zero rows is nan
+  }
+}
+
+// ---- segmentation confusion matrix -----------------------------------------------------------
+__device__ __forceinline__ int conf_class(const float (&v)[CONF_MAX_C], int C) {
+  float best = v[0];
+  int bi = 0;
+#pragma unroll
+  for (int k = 1; k < CONF_MAX_C; ++k)
+    if (k < C && argmax_beats(v[k], k, best, bi)) {
+      best = v[k];
+      bi = k;
+    }
+  return bi;
+}
+
+// the wave's pixels of cell `cell` (-1: counted nowhere) added to the lane that owns the cell
+__device__ __forceinline__ void conf_count(int cell, int cells, int lane, int &acc) {
+  for (int c = 0; c < cells; ++c) {
+    const int hits = __popcll(__ballot(cell == c));
+    acc += lane == c ? hits : 0;
+  }
+}
+
+// VEC: HW % 4 == 0 and logits 16-byte aligned: one float4 per plane per thread.  Otherwise
+// dword loads.  Both paths visit the same pixels and add integers.
+template <bool VEC>
+__global__ void __launch_bounds__(VAL_THREADS)
+    k_seg_conf_partials(const float *__restrict__ x, const long long *__restrict__ tg, int C, int HW,
+                        int ignore, int *__restrict__ partials) {
+  __shared__ int red[VAL_WAVES][CONF_CELLS];
+  const int tid = threadIdx.x, lane = tid & 63, cells = C * C;
+  const long long img = blockIdx.y;
+  const int p0 = blockIdx.x * CONF_CHUNK, p1 = min(HW, p0 + CONF_CHUNK);
+  const float *base = x + img * C * HW;
+  const long long *tb = tg + img * HW;
+  int acc = 0;
+  // every wave runs the same number of iterations with all lanes active at the ballots
+  if constexpr (VEC) {
+    for (int q = p0 + tid * 4; q - tid * 4 < p1; q += VAL_THREADS * 4) {
+      const bool in = q < p1;  // p1 - p0 is a multiple of 4 here
+      float4 v[CONF_MAX_C];
+#pragma unroll
+      for (int k = 0; k < CONF_MAX_C; ++k)
+        v[k] = in && k < C ? ld4(base + (long long)k * HW + q) : make_float4(0.f, 0.f, 0.f, 0.f);
+      long long t[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = in ? tb[q + j] : -1;
+      float px[4][CONF_MAX_C];
+#pragma unroll
+      for (int k = 0; k < CONF_MAX_C; ++k) {
+        px[0][k] = v[k].x;
+        px[1][k] = v[k].y;
+        px[2][k] = v[k].z;
+        px[3][k] = v[k].w;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool ok = in && t[j] != ignore && t[j] >= 0 && t[j] < C;
+        const int cell = ok ? (int)t[j] * C + conf_class(px[j], C) : -1;
+        conf_count(cell, cells, lane, acc);
+      }
+    }
+  } else {
+    for (int q = p0 + tid; q - tid < p1; q += VAL_THREADS) {
+      const bool in = q < p1;
+      float v[CONF_MAX_C];
+#pragma unroll
+      for (int k = 0; k < CONF_MAX_C; ++k) v[k] = in && k < C ? base[(long long)k * HW + q] : 0.f;
+      const long long t = in ? tb[q] : -1;
+      const bool ok = in && t != ignore && t >= 0 && t < C;
+      const int cell = ok ? (int)t * C + conf_class(v, C) : -1;
+      conf_count(cell, cells, lane, acc);
+    }
+  }
+  red[tid >> 6][lane] = acc;
+  __syncthreads();
+  if (tid < cells) {
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < VAL_WAVES; ++w) s += red[w][tid];
+    partials[(img * gridDim.x + blockIdx.x) * CONF_CELLS + tid] = s;
+  }
+}
+
+// one workgroup: thread (slice, cell) sums every VAL_WAVES-th workgroup's count of its cell,
+// then the slices are added in order
+__global__ void __launch_bounds__(VAL_THREADS)
+    k_seg_conf_final(const int *__restrict__ partials, int nblocks, int cells,
+                     long long *__restrict__ conf) {
+  __shared__ long long red[VAL_WAVES][CONF_CELLS];
+  const int cell = threadIdx.x & 63, slice = threadIdx.x >> 6;
+  long long s = 0;
+  if (cell < cells)
+    for (int i = slice; i < nblocks; i += VAL_WAVES) s += partials[(long long)i * CONF_CELLS + cell];
+  red[slice][cell] = s;
+  __syncthreads();
+  if (threadIdx.x < cells) {
+    long long t = 0;
+#pragma unroll
+    for (int w = 0; w < VAL_WAVES; ++w) t += red[w][threadIdx.x];
+    conf[threadIdx.x] = t;
+  }
+}
+
+// ---- epoch accumulator ------------------------------------------------------------------------
+// packed: double sums[5] (acc_steer, reverse, segmentation, depth, val_loss) | int64 batches |
+// int64 conf[cells]
+__global__ void __launch_bounds__(64)
+    k_val_accumulate(const float *__restrict__ control, const float *__restrict__ seg,
+                     const float *__restrict__ depth, const long long *__restrict__ conf, int cells,
+                     double *__restrict__ sums, long long *__restrict__ counts,
+                     float *__restrict__ val_loss) {
+  const int lane = threadIdx.x;
+  if (lane < cells) counts[1 + lane] += conf[lane];
+  if (lane == 0) {
+    const float a = control[0], r = control[1], s = seg[0], d = depth[0];
+    const float v = ((a + r) + s) + d;  // Python's sum(d.values())
+    val_loss[0] = v;
+    sums[0] += (double)a;
+    sums[1] += (double)r;
+    sums[2] += (double)s;
+    sums[3] += (double)d;
+    sums[4] += (double)v;
+    counts[0] += 1;
+  }
+}
+
+inline int conf_chunks(int HW) { return cdiv(HW, CONF_CHUNK); }
+
+}  // namespace e2ep
+
+using namespace e2ep;
+
+extern "C" {
+
+size_t e2ep_control_val_workspace(int B, int F) {
+  if (B <= 0 || F <= 0) return 0;
+  return (size_t)B * F * 4 * sizeof(float);
+}
+
+int e2ep_control_val_fwd(const float *logits, const float *gt_acc, const float *gt_steer,
+                         const long long *gt_reverse, int B, int T, int vocab, int F,
+                         int valid_token, int split, int pad, float *out, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  E2EP_REQUIRE(logits && gt_acc && gt_steer && gt_reverse && out && workspace, E2EP_EINVAL,
+               "e2ep_control_val_fwd: null argument");
+  E2EP_REQUIRE(B > 0 && T >= 5 && (T - 2) % 3 == 0 && F == (T - 2) / 3, E2EP_EINVAL,
+               "e2ep_control_val_fwd: T=%d must be 3 F + 2 with F=%d labels per sample (B=%d)", T,
+               F, B);
+  E2EP_REQUIRE(vocab > 0 && valid_token > 0 && split >= 0 && split <= vocab, E2EP_EINVAL,
+               "e2ep_control_val_fwd: bad vocabulary (vocab=%d valid_token=%d split=%d)", vocab,
+               valid_token, split);
+  E2EP_REQUIRE((long long)B * F * 3 <= 0x7fffffffLL / 4, E2EP_ERANGE,
+               "e2ep_control_val_fwd: B * F = %lld rows exceed the grid", (long long)B * F);
+  E2EP_REQUIRE(workspace_bytes >= e2ep_control_val_workspace(B, F), E2EP_EINVAL,
+               "e2ep_control_val_fwd: workspace %zu < %zu bytes", workspace_bytes,
+               e2ep_control_val_workspace(B, F));
+  E2EP_REQUIRE(((uintptr_t)logits & 3) == 0 && ((uintptr_t)gt_acc & 3) == 0 &&
+                   ((uintptr_t)gt_steer & 3) == 0 && ((uintptr_t)gt_reverse & 7) == 0 &&
+                   ((uintptr_t)out & 3) == 0 && ((uintptr_t)workspace & 3) == 0,
+               E2EP_EINVAL, "e2ep_control_val_fwd: misaligned buffer");
+  const int n = B * F;
+  float *row_vals = static_cast<float *>(workspace);
+  hipLaunchKernelGGL(k_ctrl_val_rows, dim3(cdiv((long long)n * 3, VAL_WAVES)), dim3(VAL_THREADS), 0,
+                     as_stream(stream), logits, gt_acc, gt_steer, gt_reverse, B, T, vocab, F,
+                     valid_token, split, pad, row_vals);
+  hipLaunchKernelGGL(k_ctrl_val_final, dim3(1), dim3(VAL_THREADS), 0, as_stream(stream), row_vals,
+                     n, out);
+  return launch_status("e2ep_control_val_fwd");
+}
+
+size_t e2ep_seg_confusion_workspace(int images, int HW) {
+  if (images <= 0 || HW <= 0) return 0;
+  return (size_t)images * conf_chunks(HW) * CONF_CELLS * sizeof(int);
+}
+
+int e2ep_seg_confusion(const float *logits, const long long *target, int images, int C, int HW,
+                       int ignore, int64_t *conf, void *workspace, size_t workspace_bytes,
+                       void *stream) {
+  E2EP_REQUIRE(logits && target && conf && workspace, E2EP_EINVAL,
+               "e2ep_seg_confusion: null argument");
+  E2EP_REQUIRE(C >= 2 && C <= CONF_MAX_C, E2EP_EINVAL, "e2ep_seg_confusion: C=%d outside 2..%d", C,
+               CONF_MAX_C);
+  E2EP_REQUIRE(images > 0 && HW > 0, E2EP_EINVAL, "e2ep_seg_confusion: bad shape (images=%d HW=%d)",
+               images, HW);
+  E2EP_REQUIRE(images <= 65535 && HW <= 0x7fff0000 &&
+                   (long long)images * conf_chunks(HW) <= 0x7fffffffLL / CONF_CELLS,
+               E2EP_ERANGE, "e2ep_seg_confusion: images=%d HW=%d exceed the grid", images, HW);
+  E2EP_REQUIRE(workspace_bytes >= e2ep_seg_confusion_workspace(images, HW), E2EP_EINVAL,
+               "e2ep_seg_confusion: workspace %zu < %zu bytes", workspace_bytes,
+               e2ep_seg_confusion_workspace(images, HW));
+  E2EP_REQUIRE(((uintptr_t)logits & 3) == 0 && ((uintptr_t)target & 7) == 0 &&
+                   ((uintptr_t)conf & 7) == 0 && ((uintptr_t)workspace & 3) == 0,
+               E2EP_EINVAL, "e2ep_seg_confusion: misaligned buffer");
+  const int chunks = conf_chunks(HW);
+  const dim3 grid(chunks, images), block(VAL_THREADS);
+  int *part = static_cast<int *>(workspace);
+  if (HW % 4 == 0 && ((uintptr_t)logits & 15) == 0)
+    hipLaunchKernelGGL(k_seg_conf_partials<true>, grid, block, 0, as_stream(stream), logits, target,
+                       C, HW, ignore, part);
+  else
+    hipLaunchKernelGGL(k_seg_conf_partials<false>, grid, block, 0, as_stream(stream), logits,
+                       target, C, HW, ignore, part);
+  hipLaunchKernelGGL(k_seg_conf_final, dim3(1), dim3(VAL_THREADS), 0, as_stream(stream), part,
+                     images * chunks, C * C, reinterpret_cast<long long *>(conf));
+  return launch_status("e2ep_seg_confusion");
+}
+
+int e2ep_val_accumulate(const float *control, const float *seg, const float *depth,
+                        const int64_t *conf, int C, void *packed, float *val_loss, void *stream) {
+  E2EP_REQUIRE(control && seg && depth && packed && val_loss, E2EP_EINVAL,
+               "e2ep_val_accumulate: null argument");
+  E2EP_REQUIRE(conf ? (C >= 2 && C <= CONF_MAX_C) : C == 0, E2EP_EINVAL,
+               "e2ep_val_accumulate: C=%d (2..%d with a confusion matrix, 0 without)", C,
+               CONF_MAX_C);
+  E2EP_REQUIRE(((uintptr_t)control & 3) == 0 && ((uintptr_t)seg & 3) == 0 &&
+                   ((uintptr_t)depth & 3) == 0 && ((uintptr_t)conf & 7) == 0 &&
+                   ((uintptr_t)packed & 7) == 0 && ((uintptr_t)val_loss & 3) == 0,
+               E2EP_EINVAL, "e2ep_val_accumulate: misaligned buffer");
+  double *sums = static_cast<double *>(packed);
+  hipLaunchKernelGGL(k_val_accumulate, dim3(1), dim3(64), 0, as_stream(stream), control, seg, depth,
+                     reinterpret_cast<const long long *>(conf), C * C, sums,
+                     reinterpret_cast<long long *>(sums + 5), val_loss);
+  return launch_status("e2ep_val_accumulate");
+}
+
+}  // extern "C"

@@ -1,7 +1,8 @@
 """The three training losses (reference loss/*.py) as autograd ops over the fused HIP loss
 kernels (csrc/loss.hip): two launches forward (rows/blocks -> one fixed-order final sum),
 one backward, no host synchronisation, no PyTorch arithmetic.  The nn.Module wrappers in
-loss/ keep the reference's classes and signatures."""
+loss/ keep the reference's classes and signatures.  control_val and seg_confusion are the
+validation metrics (csrc/val.hip): forward only, two launches each."""
 import torch
 
 from . import _lib
@@ -88,6 +89,79 @@ def seg_weighted_ce(pred, target, weights, ignore_index=255):
     tg = _i64(target, pred.device).view(b * s, h * w)
     wt = weights.to(device=pred.device, dtype=torch.float32).contiguous()
     return _SegCE.apply(pred.reshape(b * s, c, h, w), tg, wt, int(ignore_index))
+
+
+REVERSE_SPLIT = 101  # loss/control_loss.py:69-70: the reverse mass is split at token 101
+
+
+def control_val_out(pred, gt_acc, gt_steer, gt_reverse, token_nums):
+    """control_val's two scalars as one (2,) fp32 tensor (acc_steer, reverse)."""
+    _dev(pred)
+    if pred.dim() != 3 or pred.dtype != torch.float32:
+        raise _lib.E2EPError(f"control_val: pred must be (B, T, vocab) fp32, got {pred.dtype} "
+                             f"{tuple(pred.shape)}")
+    B, T, V = pred.shape
+    if T < 5 or (T - 2) % 3 != 0:
+        raise _lib.E2EPError(f"control_val: pred has T = {T} rows per sample, expected 3 F + 2 "
+                             "(F control triples, EOS, PAD)")
+    F = (T - 2) // 3
+    for name, t in (("gt_acc", gt_acc), ("gt_steer", gt_steer), ("gt_reverse", gt_reverse)):
+        if tuple(t.shape) != (B, F):
+            raise _lib.E2EPError(f"control_val: {name} {tuple(t.shape)} vs pred {tuple(pred.shape)}"
+                                 f" (expected {(B, F)})")
+    token_nums = int(token_nums)
+    if token_nums <= 4:
+        raise _lib.E2EPError(f"control_val: token_nums {token_nums} leaves no control tokens")
+    dev = pred.device
+    with torch.no_grad():
+        pred = pred.detach().contiguous()
+        acc = gt_acc.detach().to(device=dev, dtype=torch.float32).contiguous()
+        steer = gt_steer.detach().to(device=dev, dtype=torch.float32).contiguous()
+        rev = _i64(gt_reverse.detach(), dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.call_raw("e2ep_control_val_workspace", B, F), dtype=torch.uint8,
+                         device=dev)
+        _lib.call("e2ep_control_val_fwd", _lib.ptr(pred), _lib.ptr(acc), _lib.ptr(steer),
+                  _lib.ptr(rev), B, T, V, F, token_nums - 4, min(REVERSE_SPLIT, V), token_nums - 1,
+                  _lib.ptr(out), _lib.ptr(ws), _lib.nbytes(ws), _lib.stream())
+    return out
+
+
+def control_val(pred, gt_acc, gt_steer, gt_reverse, token_nums):
+    """loss/control_loss.py:45-75 (ControlValLoss.forward) in two launches: (acc_steer_val_loss,
+    reverse_val_loss) as device scalars.  pred (B, 3 F + 2, token_nums) fp32 logits, gt_acc and
+    gt_steer (B, F), gt_reverse (B, F) token ids.  No autograd: these are metrics.  The tokens
+    are the argmax of the logits (the reference's argmax of the fp32 softmax, except where two
+    distinct logits round to equal probabilities: csrc/val.hip)."""
+    out = control_val_out(pred, gt_acc, gt_steer, gt_reverse, token_nums)
+    return out[0], out[1]
+
+
+def seg_confusion(pred, target, ignore_index=255):
+    """The (C, C) int64 confusion matrix of segmentation logits against their labels, rows =
+    target class, columns = predicted class (the per-pixel argmax the agent steers by, in
+    torch.argmax's order).  pred (n, C, X, Y) fp32 logits, target n * X * Y class ids in any
+    shape; a pixel whose label is ignore_index or outside [0, C) is counted nowhere."""
+    _dev(pred)
+    if pred.dim() != 4 or pred.dtype != torch.float32:
+        raise _lib.E2EPError(f"seg_confusion: pred must be (n, C, X, Y) fp32, got {pred.dtype} "
+                             f"{tuple(pred.shape)}")
+    n, C, X, Y = pred.shape
+    if not 2 <= C <= 8:
+        raise _lib.E2EPError(f"seg_confusion: {C} classes, supported are 2..8")
+    if n * X * Y == 0 or target.numel() != n * X * Y:
+        raise _lib.E2EPError(f"seg_confusion: pred {tuple(pred.shape)} vs target "
+                             f"{tuple(target.shape)}")
+    dev = pred.device
+    with torch.no_grad():
+        pred = pred.detach().contiguous()
+        tg = _i64(target.detach(), dev).view(n, X * Y)
+        conf = torch.empty((C, C), dtype=torch.int64, device=dev)
+        ws = torch.empty(_lib.call_raw("e2ep_seg_confusion_workspace", n, X * Y),
+                         dtype=torch.uint8, device=dev)
+        _lib.call("e2ep_seg_confusion", _lib.ptr(pred), _lib.ptr(tg), n, C, X * Y,
+                  int(ignore_index), _lib.ptr(conf), _lib.ptr(ws), _lib.nbytes(ws), _lib.stream())
+    return conf
 
 
 def depth_onehot(gt, d_bound, down):

@@ -1046,6 +1046,64 @@ int e2ep_target_select(const float *state, const float *goal, int B, float *targ
                        void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Validation on the device (csrc/val.hip).  Additive entry points (the ABI version stays 4);
+ * fp32, fixed-order reductions, no atomics, every launch capturable, nothing read by the host.
+ *
+ *  - e2ep_control_val_fwd: ControlValLoss.forward (loss/control_loss.py:45-75; detokenize_acc
+ *    and detokenize_steer :34-43).  logits [B][T][vocab] fp32 contiguous, gt_acc and gt_steer
+ *    [B][F] fp32, gt_reverse [B][F] int64; E2EP_EINVAL unless (T - 2) % 3 == 0 and
+ *    F == (T - 2) / 3.  Rows T-2 and T-1 of a sample are not used (pred[:, :-2]); row 3f + k:
+ *      k = 0  tok = argmax of the row in torch.argmax's order (first index of the largest
+ *             value, NaN first); half = valid_token / 2.0 and acc = tok > half ? tok / half - 1
+ *             : -(tok / half - 1) in float64, rounded to fp32 (:53-55 runs detokenize_acc on
+ *             Python numbers, then np.float32); SmoothL1 (beta 1) against gt_acc[b][f] (:57);
+ *      k = 1  the same argmax; steer = (float)tok / (float)half - 1 in fp32 (:62, an int64
+ *             tensor by a Python float); SmoothL1 against gt_steer[b][f] (:64);
+ *      k = 2  the fp32 softmax of the row (:68), p_no = sum of [0, split), p_yes = sum of
+ *             [split, vocab) (:69-70, split = 101), then the cross entropy of the pair
+ *             (p_no, p_yes) used as logits (:71-73): log(exp(p_no) + exp(p_yes)) - p_target.
+ *             A row whose target is `pad` is ignored (ignore_index), and so is one whose
+ *             target is neither 0 nor 1 (torch asserts there).
+ *    out[0] = mean(acc) + mean(steer), each over B * F (:66); out[1] = sum over the counted
+ *    reverse rows / their number, NaN when there is none (as torch).  workspace:
+ *    e2ep_control_val_workspace(B, F) bytes.
+ *    One difference: the reference takes the argmax of the fp32 softmax (:51-52, :59-60),
+ *    this entry point the argmax of the logits.  They agree when the two largest logits of
+ *    a row are exactly equal (both take the first index) and when they are far enough apart
+ *    for their fp32 probabilities to differ.
+ *
+ *  - e2ep_seg_confusion: the confusion matrix of the segmentation head against its labels
+ *    (the reference reports none).  logits [images][C][HW] fp32 contiguous, target
+ *    [images][HW] int64, 2 <= C <= 8 (else E2EP_EINVAL).  conf [C][C] int64 is overwritten:
+ *    conf[t][p] = the pixels of target class t whose predicted class is p, the prediction
+ *    being the per-pixel argmax in the order of e2ep_slot_partials.  A pixel whose target is
+ *    `ignore` or outside [0, C) is counted nowhere.  int32 counts per workgroup, summed in
+ *    int64 by one workgroup; 16-byte loads along HW when HW % 4 == 0 and logits is 16-byte
+ *    aligned, dword loads otherwise: the same integers either way.  workspace:
+ *    e2ep_seg_confusion_workspace(images, HW) bytes.
+ *
+ *  - e2ep_val_accumulate: validation_step's sum and an epoch of it
+ *    (trainer/pl_trainer.py:85-114: val_loss = sum(d.values()), logged per batch).  control
+ *    [2] = (acc_steer, reverse), seg [1], depth [1] fp32 device scalars;
+ *    val_loss[0] = ((acc_steer + reverse) + seg) + depth in fp32, the order of Python's sum.
+ *    packed: double sums[5] (acc_steer, reverse, segmentation, depth, val_loss) | int64
+ *    batches | int64 conf[C][C], 48 + 8 C C bytes, 8-byte aligned: the five values are added
+ *    to the sums, `conf` (or NULL with C = 0) to the running matrix, batches incremented.
+ *    Zero `packed` to start an epoch.
+ * ------------------------------------------------------------------------------------- */
+size_t e2ep_control_val_workspace(int B, int F);
+int e2ep_control_val_fwd(const float *logits, const float *gt_acc, const float *gt_steer,
+                         const long long *gt_reverse, int B, int T, int vocab, int F,
+                         int valid_token, int split, int pad, float *out, void *workspace,
+                         size_t workspace_bytes, void *stream);
+size_t e2ep_seg_confusion_workspace(int images, int HW);
+int e2ep_seg_confusion(const float *logits, const long long *target, int images, int C, int HW,
+                       int ignore, int64_t *conf, void *workspace, size_t workspace_bytes,
+                       void *stream);
+int e2ep_val_accumulate(const float *control, const float *seg, const float *depth,
+                        const int64_t *conf, int C, void *packed, float *val_loss, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * HIP-graph surgery: replace every memset node of a captured (not yet instantiated)
  * hipGraph_t by an equivalent kernel node.  Memset nodes replay incorrectly after the first
  * launch on this ROCm stack; PyTorch's reductions capture them.  `replaced` (optional)
