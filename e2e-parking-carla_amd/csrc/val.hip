@@ -20,6 +20,12 @@
 //   k_val_accumulate  one wave: val_loss = ((acc_steer + reverse) + seg) + depth in fp32, the
 //       five values added to float64 running sums, the confusion matrix to an int64 running
 //       matrix, the batch counter incremented; one packed buffer.
+//   k_depth_metrics_partials  grid (cell chunks, images): per cell DepthLoss's class, the
+//       argmax bin and the expected depth against the ground truth's metres (the reference
+//       only draws these: trainer/pl_trainer.py:149-168); five counts and six float64 sums per
+//       workgroup.
+//   k_depth_metrics_final  one workgroup: each camera's records added by image, then chunk,
+//       written out and added to the epoch's running buffer.
 // One documented difference from the reference: it takes the argmax of the fp32 softmax, this
 // file the argmax of the logits.  The two agree whenever the row's two largest logits are
 // exactly equal (both pick the first index) and whenever they are far enough apart that their
@@ -268,11 +274,217 @@ __global__ void __launch_bounds__(64)
 
 inline int conf_chunks(int HW) { return cdiv(HW, CONF_CHUNK); }
 
+// ---- depth-head metrics -----------------------------------------------------------------------
+// One thread per cell (a down x down block of gt), one workgroup per DM_CHUNK cells of one image,
+// so a workgroup belongs to one camera (bn % N).  A partial record is DM_SUMS doubles followed
+// by DM_COUNTS int64, in the order of e2ep.h; k_depth_metrics_final adds each camera's records
+// by image, then chunk.
+constexpr int DM_CHUNK = VAL_THREADS;  // cells per workgroup
+constexpr int DM_SUMS = 6, DM_COUNTS = 5, DM_REC = DM_SUMS + DM_COUNTS;
+constexpr int DM_MAX_CAMS = 16;
+static_assert(DM_MAX_CAMS * DM_REC <= VAL_THREADS, "k_depth_metrics_final: one thread per entry");
+
+template <typename T, int V> using dm_vec = T __attribute__((ext_vector_type(V)));
+
+// the block's value of thread v in lane 0 of wave 0: xor butterflies, then the waves in order
+template <typename A>
+__device__ __forceinline__ A dm_block_sum(A v, A *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  A t = red[0];
+#pragma unroll
+  for (int i = 1; i < VAL_WAVES; ++i) t += red[i];
+  return t;
+}
+
+// T: the ground truth's type, as k_depth_bce_fwd<T> (loss.hip), whose class statement this
+// repeats.  VEC: 16-byte loads of gt (down, W multiples of 16 / sizeof(T) elements and gt
+// 16-byte aligned), otherwise element loads; the min does not depend on the order.
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(VAL_THREADS)
+    k_depth_metrics_partials(const float *__restrict__ prob, const T *__restrict__ gt, int D, int H,
+                             int W, int down, T lo, T step, double d0, double dstep,
+                             float *__restrict__ pred_map, float *__restrict__ gt_map,
+                             int *__restrict__ cls_out, double *__restrict__ partials) {
+  __shared__ double red_d[VAL_WAVES];
+  __shared__ long long red_i[VAL_WAVES];
+  constexpr int V = 16 / (int)sizeof(T);
+  const int h = H / down, w = W / down, hw = h * w;
+  const long long bn = blockIdx.y;
+  const int pix = blockIdx.x * DM_CHUNK + threadIdx.x;
+  double s[DM_SUMS] = {0., 0., 0., 0., 0., 0.};
+  long long n[DM_COUNTS] = {0, 0, 0, 0, 0};
+  if (pix < hw) {
+    const int ci = pix / w, cj = pix - ci * w;
+    const T *g = gt + (bn * H + (long long)ci * down) * W + (long long)cj * down;
+    T mn = T(1e5);
+    for (int r = 0; r < down; ++r) {
+      if constexpr (VEC) {
+        for (int c = 0; c < down; c += V) {
+          const dm_vec<T, V> d = *reinterpret_cast<const dm_vec<T, V> *>(g + (long long)r * W + c);
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            const T e = d[j] == T(0) ? T(1e5) : d[j];
+            mn = e < mn ? e : mn;
+          }
+        }
+      } else {
+        for (int c = 0; c < down; ++c) {
+          const T d = g[(long long)r * W + c];
+          const T e = d == T(0) ? T(1e5) : d;
+          mn = e < mn ? e : mn;
+        }
+      }
+    }
+    const T b = (mn - lo) / step;
+    const int k = (b < T(D + 1) && b >= T(0)) ? (int)b : 0;
+    const long long cell = bn * hw + pix;
+    if (cls_out) cls_out[cell] = k;
+    if (gt_map) gt_map[cell] = k >= 1 ? (float)mn : 0.f;
+    if (k >= 1 || pred_map) {
+      const float *pp = prob + bn * D * hw + pix;
+      const int t = k - 1;
+      float best = pp[0], pt = best;
+      int a = 0;
+      double ze = (double)best * d0;
+      for (int d = 1; d < D; ++d) {
+        const float p = pp[(long long)d * hw];
+        if (argmax_beats(p, d, best, a)) best = p, a = d;
+        pt = d == t ? p : pt;
+        ze += (double)p * (d0 + (double)d * dstep);
+      }
+      const double za = d0 + (double)a * dstep;
+      if (pred_map) pred_map[cell] = (float)za;
+      if (k >= 1) {
+        const double gm = (double)mn, ea = fabs(za - gm), ee = fabs(ze - gm);
+        const int db = a > t ? a - t : t - a;
+        n[0] = 1;
+        n[1] = db == 0;
+        n[2] = db <= 1;
+        n[3] = db;
+        n[4] = za < 1.25 * gm && gm < 1.25 * za;
+        s[0] = ea;
+        s[1] = (za - gm) * (za - gm);
+        s[2] = ea / gm;
+        s[3] = ee;
+        s[4] = (ze - gm) * (ze - gm);
+        s[5] = (double)pt;
+      }
+    }
+  }
+  double *rec = partials + (bn * gridDim.x + blockIdx.x) * DM_REC;
+#pragma unroll
+  for (int e = 0; e < DM_SUMS; ++e) {
+    const double v = dm_block_sum(s[e], red_d);
+    if (threadIdx.x == 0) rec[e] = v;
+  }
+#pragma unroll
+  for (int e = 0; e < DM_COUNTS; ++e) {
+    const long long v = dm_block_sum(n[e], red_i);
+    if (threadIdx.x == 0) reinterpret_cast<long long *>(rec)[DM_SUMS + e] = v;
+  }
+}
+
+// one workgroup: thread (camera, entry) adds the camera's records image by image, chunk by
+// chunk, writes out and adds it to running.  out / running: double sums[N][6] | int64
+// counts[N][5] (| int64 batches)
+__global__ void __launch_bounds__(VAL_THREADS)
+    k_depth_metrics_final(const double *__restrict__ partials, int BN, int N, int chunks,
+                          double *__restrict__ out, double *__restrict__ running) {
+  const int cam = threadIdx.x / DM_REC, e = threadIdx.x - cam * DM_REC;
+  if (cam < N) {
+    if (e < DM_SUMS) {
+      double v = 0.;
+      for (int bn = cam; bn < BN; bn += N)
+        for (int c = 0; c < chunks; ++c) v += partials[((long long)bn * chunks + c) * DM_REC + e];
+      out[cam * DM_SUMS + e] = v;
+      if (running) running[cam * DM_SUMS + e] += v;
+    } else {
+      const long long *pi = reinterpret_cast<const long long *>(partials);
+      const int slot = N * DM_SUMS + cam * DM_COUNTS + (e - DM_SUMS);
+      long long v = 0;
+      for (int bn = cam; bn < BN; bn += N)
+        for (int c = 0; c < chunks; ++c) v += pi[((long long)bn * chunks + c) * DM_REC + e];
+      reinterpret_cast<long long *>(out)[slot] = v;
+      if (running) reinterpret_cast<long long *>(running)[slot] += v;
+    }
+  }
+  if (threadIdx.x == 0 && running) reinterpret_cast<long long *>(running)[N * DM_REC] += 1;
+}
+
+inline bool dm_shape_ok(int BN, int N, int H, int W, int down) {
+  return N >= 1 && N <= DM_MAX_CAMS && BN > 0 && BN % N == 0 && down > 0 && H > 0 && W > 0 &&
+         H % down == 0 && W % down == 0;
+}
+inline int dm_chunks(int H, int W, int down) {
+  return cdiv((long long)(H / down) * (W / down), DM_CHUNK);
+}
+
 }  // namespace e2ep
 
 using namespace e2ep;
 
+template <typename T>
+static int depth_metrics(const char *name, const float *prob, const T *gt, int BN, int N, int D,
+                         int H, int W, int down, T lo, T step, double d0, double dstep, void *out,
+                         void *running, float *pred_map, float *gt_map, int *cls_out,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+  E2EP_REQUIRE(prob && gt && out && workspace, E2EP_EINVAL, "%s: null argument", name);
+  E2EP_REQUIRE(dm_shape_ok(BN, N, H, W, down) && D > 0, E2EP_EINVAL,
+               "%s: bad shape (BN=%d N=%d (1..%d, dividing BN) D=%d H=%d W=%d down=%d)", name, BN,
+               N, DM_MAX_CAMS, D, H, W, down);
+  E2EP_REQUIRE(BN <= 65535 && (long long)(H / down) * (W / down) <= 0x7fff0000LL, E2EP_ERANGE,
+               "%s: BN=%d images of %d x %d cells exceed the grid", name, BN, H / down, W / down);
+  E2EP_REQUIRE(workspace_bytes >= e2ep_depth_metrics_workspace(BN, N, H, W, down), E2EP_EINVAL,
+               "%s: workspace %zu < %zu bytes", name, workspace_bytes,
+               e2ep_depth_metrics_workspace(BN, N, H, W, down));
+  E2EP_REQUIRE(((uintptr_t)prob & 3) == 0 && (uintptr_t)gt % sizeof(T) == 0 &&
+                   ((uintptr_t)out & 7) == 0 && ((uintptr_t)running & 7) == 0 &&
+                   ((uintptr_t)pred_map & 3) == 0 && ((uintptr_t)gt_map & 3) == 0 &&
+                   ((uintptr_t)cls_out & 3) == 0 && ((uintptr_t)workspace & 7) == 0,
+               E2EP_EINVAL, "%s: misaligned buffer", name);
+  constexpr int V = 16 / (int)sizeof(T);
+  const int chunks = dm_chunks(H, W, down);
+  const dim3 grid(chunks, BN), block(VAL_THREADS);
+  double *part = static_cast<double *>(workspace);
+  if (down % V == 0 && W % V == 0 && ((uintptr_t)gt & 15) == 0)
+    hipLaunchKernelGGL((k_depth_metrics_partials<T, true>), grid, block, 0, as_stream(stream), prob,
+                       gt, D, H, W, down, lo, step, d0, dstep, pred_map, gt_map, cls_out, part);
+  else
+    hipLaunchKernelGGL((k_depth_metrics_partials<T, false>), grid, block, 0, as_stream(stream),
+                       prob, gt, D, H, W, down, lo, step, d0, dstep, pred_map, gt_map, cls_out,
+                       part);
+  hipLaunchKernelGGL(k_depth_metrics_final, dim3(1), dim3(VAL_THREADS), 0, as_stream(stream), part,
+                     BN, N, chunks, static_cast<double *>(out), static_cast<double *>(running));
+  return launch_status(name);
+}
+
 extern "C" {
+
+size_t e2ep_depth_metrics_workspace(int BN, int N, int H, int W, int down) {
+  if (!dm_shape_ok(BN, N, H, W, down)) return 0;
+  return (size_t)BN * dm_chunks(H, W, down) * DM_REC * sizeof(double);
+}
+
+int e2ep_depth_metrics(const float *prob, const float *gt, int BN, int N, int D, int H, int W,
+                       int down, float lo, float step, double d0, double dstep, void *out,
+                       void *running, float *pred_map, float *gt_map, int *cls_out,
+                       void *workspace, size_t workspace_bytes, void *stream) {
+  return depth_metrics("e2ep_depth_metrics", prob, gt, BN, N, D, H, W, down, lo, step, d0, dstep,
+                       out, running, pred_map, gt_map, cls_out, workspace, workspace_bytes, stream);
+}
+
+int e2ep_depth_metrics_f64(const float *prob, const double *gt, int BN, int N, int D, int H, int W,
+                           int down, double lo, double step, double d0, double dstep, void *out,
+                           void *running, float *pred_map, float *gt_map, int *cls_out,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+  return depth_metrics("e2ep_depth_metrics_f64", prob, gt, BN, N, D, H, W, down, lo, step, d0,
+                       dstep, out, running, pred_map, gt_map, cls_out, workspace, workspace_bytes,
+                       stream);
+}
 
 size_t e2ep_control_val_workspace(int B, int F) {
   if (B <= 0 || F <= 0) return 0;

@@ -1,8 +1,8 @@
 """The three training losses (reference loss/*.py) as autograd ops over the fused HIP loss
 kernels (csrc/loss.hip): two launches forward (rows/blocks -> one fixed-order final sum),
 one backward, no host synchronisation, no PyTorch arithmetic.  The nn.Module wrappers in
-loss/ keep the reference's classes and signatures.  control_val and seg_confusion are the
-validation metrics (csrc/val.hip): forward only, two launches each."""
+loss/ keep the reference's classes and signatures.  control_val, seg_confusion and
+depth_metrics are the validation metrics (csrc/val.hip): forward only, two launches each."""
 import torch
 
 from . import _lib
@@ -219,3 +219,68 @@ def depth_bce(prob, gt, d_bound, down):
     g = gt.to(device=prob.device, dtype=dt, non_blocking=True).contiguous()
     lo = float(d_bound[0] - d_bound[2])  # evaluated in Python double, applied in the gt dtype
     return _DepthBCE.apply(prob, g, int(down), lo, float(d_bound[2]))
+
+
+DEPTH_SUMS, DEPTH_COUNTS = 6, 5  # per camera: float64 sums and int64 counts (csrc/val.hip)
+
+
+def depth_metrics_bytes(n_cams, running=False):
+    """Bytes of depth_metrics' `out` buffer for n_cams cameras, or of a `running` buffer (the
+    same layout followed by the int64 batch counter)."""
+    return 8 * (DEPTH_SUMS + DEPTH_COUNTS) * int(n_cams) + (8 if running else 0)
+
+
+def depth_metrics(prob, gt, d_bound, down, n_cams, running=None, maps=False):
+    """What the depth head predicts against the ground truth, per camera, in two launches
+    (csrc/val.hip; the reference only draws it: trainer/pl_trainer.py:149-168, log_depth).
+    prob (B*N, D, H/down, W/down) probabilities, gt (B, N, H, W) metric depth, as depth_bce; image
+    bn belongs to camera bn % n_cams.  Per foreground cell of DepthLoss (class k >= 1, true bin
+    t = k - 1, g = the cell's smallest non-zero depth in metres) with a = the argmax bin,
+    z_a = d_bound[0] + a * d_bound[2] (log_depth's metres, the frustum's depth of that bin) and
+    z_e = the distribution's expected depth, all in float64:
+        sums    |z_a - g|, (z_a - g)^2, |z_a - g| / g, |z_e - g|, (z_e - g)^2, p_t
+        counts  cells, a == t, |a - t| <= 1, sum |a - t|, z_a < 1.25 g and g < 1.25 z_a
+    g lies in [z_t, z_t + step), so a perfect argmax still has |z_a - g| of about step / 2.
+    Returns `out`, a uint8 tensor of depth_metrics_bytes(n_cams) bytes holding this call alone:
+    float64 sums[N][6] | int64 counts[N][5] (ValStep.unpack_depth reads it).  `running`, a
+    zeroed uint8 tensor of depth_metrics_bytes(n_cams, running=True) bytes, has every entry of
+    `out` added to it and its batch counter incremented.  maps=True returns (out, pred_map,
+    gt_map, cls): z_a and g (0 for a background cell) as (B*N, H/down, W/down) fp32 and the
+    class k as int32, log_depth's two panels at cell resolution.  No autograd, no host read."""
+    _dev(prob, running)
+    if gt.dim() != 4 or prob.dim() != 4 or prob.dtype != torch.float32:
+        raise _lib.E2EPError(f"depth_metrics: prob must be (B*N, D, h, w) fp32 and gt (B, N, H, W),"
+                             f" got {prob.dtype} {tuple(prob.shape)} and {tuple(gt.shape)}")
+    B, N, H, W = gt.shape
+    D = int((d_bound[1] - d_bound[0]) / d_bound[2])
+    down, n_cams = int(down), int(n_cams)
+    if down <= 0 or prob.shape != (B * N, D, H // down, W // down) or H % down or W % down:
+        raise _lib.E2EPError(f"depth_metrics: prob {tuple(prob.shape)} vs gt {tuple(gt.shape)}")
+    if not 1 <= n_cams <= 16 or (B * N) % n_cams:
+        raise _lib.E2EPError(f"depth_metrics: {n_cams} cameras (1..16, dividing the {B * N} "
+                             "images)")
+    if running is not None and (running.dtype != torch.uint8 or not running.is_contiguous()
+                                or running.numel() != depth_metrics_bytes(n_cams, True)):
+        raise _lib.E2EPError(f"depth_metrics: running must be {depth_metrics_bytes(n_cams, True)} "
+                             f"contiguous uint8 bytes for {n_cams} cameras")
+    dev = prob.device
+    dt = torch.float64 if gt.dtype == torch.float64 else torch.float32  # as depth_bce
+    lo = float(d_bound[0] - d_bound[2])
+    with torch.no_grad():
+        prob = prob.detach().contiguous()
+        g = gt.detach().to(device=dev, dtype=dt, non_blocking=True).contiguous()
+        out = torch.empty(depth_metrics_bytes(n_cams), dtype=torch.uint8, device=dev)
+        pred_map = gt_map = cls = None
+        if maps:
+            shape = (B * N, H // down, W // down)
+            pred_map = torch.empty(shape, dtype=torch.float32, device=dev)
+            gt_map = torch.empty(shape, dtype=torch.float32, device=dev)
+            cls = torch.empty(shape, dtype=torch.int32, device=dev)
+        ws = torch.empty(_lib.call_raw("e2ep_depth_metrics_workspace", B * N, n_cams, H, W, down),
+                         dtype=torch.uint8, device=dev)
+        fn = "e2ep_depth_metrics_f64" if dt == torch.float64 else "e2ep_depth_metrics"
+        _lib.call(fn, _lib.ptr(prob), _lib.ptr(g), B * N, n_cams, D, H, W, down, lo,
+                  float(d_bound[2]), float(d_bound[0]), float(d_bound[2]), _lib.ptr(out),
+                  _lib.ptr(running), _lib.ptr(pred_map), _lib.ptr(gt_map), _lib.ptr(cls),
+                  _lib.ptr(ws), _lib.nbytes(ws), _lib.stream())
+    return (out, pred_map, gt_map, cls) if maps else out

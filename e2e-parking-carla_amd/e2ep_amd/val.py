@@ -13,6 +13,8 @@ ModelCheckpoint(monitor='val_loss') selects checkpoints by.  ValStep runs
     losses.seg_confusion                         two launches: the BEV head's confusion matrix
     e2ep_val_accumulate                          one launch: val_loss, and the epoch's running
                                                  sums, matrix and batch counter on the device
+    losses.depth_metrics                         with depth_metrics=True, after the depth loss:
+                                                 two launches, the depth head per camera
 
 as one replayed HIP graph (graph=True) or the same calls eagerly (graph=False).  No call reads
 anything back; result() makes the epoch's one device-to-host copy.
@@ -34,6 +36,17 @@ buffers with one all-reduce (SUM) before it reads them, staged through the host 
 TrainStep._allreduce stages the gradients.  The integer counts travel as float64 in that one
 collective, exact below 2^53.
 
+Depth metrics (depth_metrics=True): the depth head's softmax is the lift-splat weight of every
+camera feature, and its BCE does not say whether a camera puts its mass in the right bin.  Per
+camera and overall, over DepthLoss's foreground cells: how often the argmax bin is the true one
+(depth_bin_acc, depth_bin_within1, depth_bin_mae in bins), the argmax depth z_a against the
+cell's metres g (depth_abs_err, depth_rmse, depth_abs_rel, depth_delta125: the share of cells
+with max(z_a / g, g / z_a) < 1.25), the distribution's expected depth against g
+(depth_exp_abs_err, depth_exp_rmse) and the mass on the true bin (depth_true_bin_prob).  g lies
+in [z_t, z_t + step) while a bin's depth is its lower edge z_t, so a perfect argmax still has
+depth_abs_err of about step / 2.  The sums live in a second packed buffer, packed_depth, which
+shares packed's allocation, copy, zeroing and all-reduce.
+
 ParkingTrainingModule.validation_step and ControlValLoss remain as the Lightning-compatible
 path; this module does not change them."""
 import numpy as np
@@ -47,6 +60,12 @@ KEYS = ("acc_steer_val_loss", "reverse_val_loss", "segmentation_val_loss", "dept
         "val_loss")  # the reference's logged names, in the packed buffer's order
 _RIG = ("intrinsics", "extrinsics")
 _HEAD = 8 * (len(KEYS) + 1)  # bytes of the float64 sums and the int64 batch counter
+# finish_depth's keys beside depth_cells: (name, index of the numerator, 's'um or 'c'ount, sqrt)
+_DEPTH = (("depth_bin_acc", 1, "c", False), ("depth_bin_within1", 2, "c", False),
+          ("depth_bin_mae", 3, "c", False), ("depth_delta125", 4, "c", False),
+          ("depth_abs_err", 0, "s", False), ("depth_rmse", 1, "s", True),
+          ("depth_abs_rel", 2, "s", False), ("depth_exp_abs_err", 3, "s", False),
+          ("depth_exp_rmse", 4, "s", True), ("depth_true_bin_prob", 5, "s", False))
 
 
 class ValStep:
@@ -55,10 +74,14 @@ class ValStep:
     `batch`: a reference-schema batch; its tensors (the rig aside) become the step's static
     device inputs, and a later call's batch is copied into them.  `confusion=False` leaves the
     segmentation confusion matrix (and IoU) out.  `world` > 1 makes result() merge the ranks.
+    `depth_metrics=True` adds the per-camera depth metrics (losses.depth_metrics) to the chain
+    and to result(); `depth_maps=True` also keeps the last batch's argmax-depth, ground-truth
+    and class maps at cell resolution in `self.depth_maps`.
     Constructing the object accumulates nothing: the warm-up runs and the capture leave the
     packed buffer zero."""
 
-    def __init__(self, module, batch, noise=None, world=1, graph=True, warmup=2, confusion=True):
+    def __init__(self, module, batch, noise=None, world=1, graph=True, warmup=2, confusion=True,
+                 depth_metrics=False, depth_maps=False):
         p = next(module.parameters(), None)
         if p is None or not p.is_cuda:
             raise _lib.E2EPError("ValStep: the module must be on the HIP device (there is no "
@@ -72,12 +95,23 @@ class ValStep:
         self._use_noise = noise is not None
         self.noise = noise.to(device=dev, dtype=torch.float32).clone() if self._use_noise else None
         self.C = int(module.cfg.seg_classes) if self.confusion else 0
-        self.packed = torch.zeros(_HEAD + 8 * self.C * self.C, dtype=torch.uint8, device=dev)
-        self._host = torch.zeros(self.packed.numel(), dtype=torch.uint8).pin_memory()
+        self.depth_metrics, self._want_maps = bool(depth_metrics), bool(depth_maps)
+        if self._want_maps and not self.depth_metrics:
+            raise _lib.E2EPError("ValStep: depth_maps=True needs depth_metrics=True")
+        self.cams = int(self.batch["depth"].shape[1]) if self.depth_metrics else 0
+        n = _HEAD + 8 * self.C * self.C
+        nd = losses.depth_metrics_bytes(self.cams, running=True) if self.depth_metrics else 0
+        # one allocation, so one fill zeroes and one copy reads both packed buffers
+        self._buf = torch.zeros(n + nd, dtype=torch.uint8, device=dev)
+        self.packed = self._buf[:n]
+        self.packed_depth = self._buf[n:] if self.depth_metrics else None
+        self._host = torch.zeros(n + nd, dtype=torch.uint8).pin_memory()
         self.val_loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.pred = None  # (pred_control, pred_segmentation, pred_depth) of the last batch
         self.values = None  # device scalars of the last batch, by KEYS[:4]
         self.conf = None  # (C, C) int64 of the last batch
+        self.depth_out = None  # losses.depth_metrics' buffer of the last batch
+        self.depth_maps = None  # (pred_map, gt_map, cls) of the last batch, with depth_maps=True
         self._rig = _rig_key(batch)
         self._graph = None
         self._plans = []
@@ -101,6 +135,12 @@ class ValStep:
                                               batch["gt_reverse"], mod.cfg.token_nums)
                 seg = mod.segmentation_loss_func(ps.unsqueeze(1), batch["segmentation"])
                 depth = mod.depth_loss_func(pd, batch["depth"])
+                dm = None
+                if self.depth_metrics:
+                    dl = mod.depth_loss_func
+                    dm = losses.depth_metrics(pd, batch["depth"], dl.d_bound, dl.down_sample_factor,
+                                              self.cams, running=self.packed_depth,
+                                              maps=self._want_maps)
                 conf = None
                 if self.confusion:
                     conf = losses.seg_confusion(ps, batch["segmentation"],
@@ -112,6 +152,10 @@ class ValStep:
             if was_training:
                 mod.train()
         self.pred, self.conf = (pc, ps, pd), conf
+        if self._want_maps:
+            self.depth_out, self.depth_maps = dm[0], dm[1:]
+        else:
+            self.depth_out = dm
         self.values = {"acc_steer_val_loss": ctrl[0], "reverse_val_loss": ctrl[1],
                        "segmentation_val_loss": seg, "depth_val_loss": depth}
         return self.val_loss
@@ -122,7 +166,7 @@ class ValStep:
         with torch.cuda.stream(s):
             for _ in range(max(warmup, 1)):  # fills every cache the capture reuses
                 self._run()
-            self.packed.zero_()  # the warm-up is not part of an epoch
+            self._buf.zero_()  # the warm-up is not part of an epoch
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         self._graph, _, self.graph_memsets = graphs.capture(self._run)
@@ -154,39 +198,69 @@ class ValStep:
         return self._run()
 
     def reset(self):
-        """Start an epoch: zero the running sums, the confusion matrix and the counter."""
-        self.packed.zero_()
+        """Start an epoch: zero the running sums, the confusion matrix and the counter (and the
+        depth metrics' packed buffer, which shares the allocation)."""
+        self._buf.zero_()
 
     def _merge(self):
         """The ranks' packed buffers added into a host copy: one all-reduce (SUM), the counts
         as float64 beside the sums (once per epoch, outside the captured chain: the RCCL path
         forms that vector with two small torch ops on the device)."""
+        return self._merge_all()[0]
+
+    def _merge_all(self):
+        """_merge for both packed buffers, (packed, packed_depth or None): the depth metrics'
+        sums and counts ride behind the others in the same all-reduce."""
+        ns = self.cams * losses.DEPTH_SUMS  # float64 sums at the head of packed_depth
         if dist.get_backend() == "nccl":
             sums = self.packed[:_HEAD - 8].view(torch.float64)
             counts = self.packed[_HEAD - 8:].view(torch.int64)
-            flat = torch.cat([sums, counts.to(torch.float64)])
+            parts = [sums, counts.to(torch.float64)]
+            if self.depth_metrics:
+                parts += [self.packed_depth[:8 * ns].view(torch.float64),
+                          self.packed_depth[8 * ns:].view(torch.int64).to(torch.float64)]
+            flat = torch.cat(parts)
             dist.all_reduce(flat)
             flat = flat.cpu()
         else:  # gloo: staged through the host, the ordering explicit
-            self._host.copy_(self.packed, non_blocking=True)
+            self._host.copy_(self._buf, non_blocking=True)
             torch.cuda.current_stream().synchronize()
-            sums, batches, conf = self.unpack(self._host.numpy())
+            host = self._host.numpy()
+            sums, batches, conf = self.unpack(host[:self.packed.numel()])
             counts = np.concatenate([[batches], conf.reshape(-1) if conf is not None else []])
-            flat = torch.from_numpy(np.concatenate([sums, counts.astype(np.float64)]))
+            parts = [sums, counts.astype(np.float64)]
+            if self.depth_metrics:
+                dsums, dcounts, dbatches = self.unpack_depth(host[self.packed.numel():])
+                parts += [dsums.reshape(-1), dcounts.reshape(-1).astype(np.float64),
+                          np.asarray([dbatches], dtype=np.float64)]
+            flat = torch.from_numpy(np.concatenate(parts))
             dist.all_reduce(flat)
         flat = flat.numpy()
-        n = len(KEYS)
-        conf = np.rint(flat[n + 1:]).astype(np.int64).reshape(self.C, self.C) if self.C else None
-        return self.pack(flat[:n], int(round(flat[n])), conf)
+        n, cells = len(KEYS), self.C * self.C
+        conf = (np.rint(flat[n + 1:n + 1 + cells]).astype(np.int64).reshape(self.C, self.C)
+                if self.C else None)
+        packed = self.pack(flat[:n], int(round(flat[n])), conf)
+        if not self.depth_metrics:
+            return packed, None
+        d = flat[n + 1 + cells:]
+        dcounts = np.rint(d[ns:]).astype(np.int64)
+        return packed, self.pack_depth(d[:ns].reshape(self.cams, -1),
+                                       dcounts[:-1].reshape(self.cams, -1), int(dcounts[-1]))
 
     def result(self):
         """The epoch so far: one device-to-host copy (after one all-reduce when world > 1),
-        then finish()."""
+        then finish(), and with depth_metrics=True finish_depth() merged into the same dict."""
         if self.world > 1:
-            return self.finish(self._merge())
-        self._host.copy_(self.packed, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return self.finish(self._host.numpy().copy())
+            packed, packed_depth = self._merge_all()
+        else:
+            self._host.copy_(self._buf, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            host = self._host.numpy().copy()
+            packed, packed_depth = host[:self.packed.numel()], host[self.packed.numel():]
+        out = self.finish(packed)
+        if self.depth_metrics:
+            out.update(self.finish_depth(packed_depth))
+        return out
 
     # -- host arithmetic on the packed buffer ------------------------------------------------
     @staticmethod
@@ -228,4 +302,59 @@ class ValStep:
             out["seg_confusion"] = conf
             out["seg_iou"] = iou
             out["seg_miou"] = float(iou[union > 0].mean()) if (union > 0).any() else float("nan")
+        return out
+
+    @staticmethod
+    def pack_depth(sums, counts, batches):
+        """The depth metrics' packed buffer (uint8 array) from the (N, 6) float64 sums, the
+        (N, 5) int64 counts (losses.depth_metrics' order) and the batch count."""
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        N = sums.shape[0] if sums.ndim == 2 else -1
+        if (N < 1 or sums.shape != (N, losses.DEPTH_SUMS)
+                or counts.shape != (N, losses.DEPTH_COUNTS)):
+            raise _lib.E2EPError(f"ValStep: depth sums {sums.shape} and counts {counts.shape} are "
+                                 f"not (N, {losses.DEPTH_SUMS}) and (N, {losses.DEPTH_COUNTS})")
+        tail = np.asarray([batches], dtype=np.int64)
+        return np.concatenate([sums.reshape(-1).view(np.uint8), counts.reshape(-1).view(np.uint8),
+                               tail.view(np.uint8)])
+
+    @staticmethod
+    def unpack_depth(packed_depth):
+        """(sums float64 (N, 6), counts int64 (N, 5), batches int) of a depth packed buffer; of
+        one batch's `depth_out` (no counter behind it) batches is None."""
+        raw = np.ascontiguousarray(np.asarray(packed_depth, dtype=np.uint8).reshape(-1))
+        per = losses.depth_metrics_bytes(1)
+        N, rest = divmod(raw.size, per)
+        if N < 1 or rest not in (0, 8):
+            raise _lib.E2EPError(f"ValStep: {raw.size} bytes are no packed depth-metrics buffer")
+        ns = 8 * N * losses.DEPTH_SUMS
+        sums = raw[:ns].view(np.float64).reshape(N, -1).copy()
+        counts = raw[ns:N * per].view(np.int64).reshape(N, -1).copy()
+        return sums, counts, (int(raw[N * per:].view(np.int64)[0]) if rest else None)
+
+    @staticmethod
+    def finish_depth(packed_depth):
+        """Epoch results of the depth metrics from their packed buffer's bytes, on the host:
+        depth_cells and the ten ratios of the module docstring over all cameras (the cameras'
+        sums added in order), and `depth_per_camera`, the same keys as arrays of length N.  A
+        ratio is NaN where there is no cell."""
+        sums, counts, _ = ValStep.unpack_depth(packed_depth)
+
+        def ratios(s, c):
+            cells = c[..., 0].astype(np.float64)
+            out = {"depth_cells": c[..., 0].copy()}
+            for key, i, kind, root in _DEPTH:
+                num = (s if kind == "s" else c)[..., i].astype(np.float64)
+                v = np.full(cells.shape, np.nan)
+                np.divide(num, cells, out=v, where=cells > 0)
+                out[key] = np.sqrt(v) if root else v
+            return out
+
+        total_s = np.zeros(losses.DEPTH_SUMS)
+        for row in sums:
+            total_s = total_s + row
+        out = {k: (int(v) if k == "depth_cells" else float(v))
+               for k, v in ratios(total_s, counts.sum(0)).items()}
+        out["depth_per_camera"] = ratios(sums, counts)
         return out

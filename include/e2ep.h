@@ -1090,6 +1090,31 @@ int e2ep_target_select(const float *state, const float *goal, int B, float *targ
  *    batches | int64 conf[C][C], 48 + 8 C C bytes, 8-byte aligned: the five values are added
  *    to the sums, `conf` (or NULL with C = 0) to the running matrix, batches incremented.
  *    Zero `packed` to start an epoch.
+ *
+ *  - e2ep_depth_metrics (_f64: gt and the bin arithmetic in double, as e2ep_depth_bce_fwd_f64):
+ *    what the depth head predicts against the ground truth, per camera (the reference only
+ *    draws it: trainer/pl_trainer.py:149-168, log_depth).  prob [BN][D][h][w] fp32
+ *    probabilities (h = H / down, w = W / down), gt [BN][H][W] metres; image bn belongs to
+ *    camera bn % N.  E2EP_EINVAL unless 1 <= N <= 16, BN % N == 0, D > 0, down > 0,
+ *    H % down == 0 and W % down == 0.  Per cell (one down x down block of gt):
+ *      mn = the block's minimum with 0 read as 1e5, b = (mn - lo) / step,
+ *      k = (b < D + 1 && b >= 0) ? (int)b : 0, all in gt's type: e2ep_depth_bce_fwd's class.
+ *      The cell is counted iff k >= 1 (DepthLoss's foreground mask); t = k - 1, g = (double)mn;
+ *      a = the argmax over the D probabilities in torch.argmax's order (NaN first);
+ *      z_a = d0 + a * dstep and z_e = sum over d ascending of (double)p_d * (d0 + d * dstep),
+ *      in double, every product and sum rounded once.
+ *    out (overwritten, this call alone): double sums[N][6] | int64 counts[N][5], 88 N bytes:
+ *      sums    |z_a - g|, (z_a - g)^2, |z_a - g| / g, |z_e - g|, (z_e - g)^2, (double)p_t
+ *      counts  cells, a == t, |a - t| <= 1, sum |a - t|, z_a < 1.25 g && g < 1.25 z_a
+ *    running (or NULL): the same layout followed by int64 batches, 88 N + 8 bytes; every entry
+ *    of out is added to it with one add and batches is incremented.  Zero it to start an epoch.
+ *    Optional [BN][h][w] outputs (NULL to skip): pred_map = (float)z_a of every cell, gt_map =
+ *    (float)g of a counted cell and 0 elsewhere, cls_out = k.  Two launches: one workgroup per
+ *    256 cells of one image writes a record to the workspace, then one workgroup adds each
+ *    camera's records by image, then chunk; no atomics.  gt is read with 16-byte loads when
+ *    down and W are multiples of 16 / sizeof(gt element) and gt is 16-byte aligned, element by
+ *    element otherwise: the same cells and values.  out, running and workspace 8-byte aligned;
+ *    workspace: e2ep_depth_metrics_workspace(BN, N, H, W, down) bytes (0 for a bad shape).
  * ------------------------------------------------------------------------------------- */
 size_t e2ep_control_val_workspace(int B, int F);
 int e2ep_control_val_fwd(const float *logits, const float *gt_acc, const float *gt_steer,
@@ -1102,6 +1127,15 @@ int e2ep_seg_confusion(const float *logits, const long long *target, int images,
                        void *stream);
 int e2ep_val_accumulate(const float *control, const float *seg, const float *depth,
                         const int64_t *conf, int C, void *packed, float *val_loss, void *stream);
+size_t e2ep_depth_metrics_workspace(int BN, int N, int H, int W, int down);
+int e2ep_depth_metrics(const float *prob, const float *gt, int BN, int N, int D, int H, int W,
+                       int down, float lo, float step, double d0, double dstep, void *out,
+                       void *running, float *pred_map, float *gt_map, int *cls_out,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int e2ep_depth_metrics_f64(const float *prob, const double *gt, int BN, int N, int D, int H, int W,
+                           int down, double lo, double step, double d0, double dstep, void *out,
+                           void *running, float *pred_map, float *gt_map, int *cls_out,
+                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * HIP-graph surgery: replace every memset node of a captured (not yet instantiated)

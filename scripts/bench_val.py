@@ -12,6 +12,9 @@ settings are called in alternating blocks so clock and thermal drift hit them al
     valstep_eager  ValStep(graph=False): the e2ep metric kernels and the device accumulator,
                    the forward still launch by launch
     valstep_graph  ValStep(graph=True): one replayed HIP graph
+    valstep_eager_depth, valstep_graph_depth  (--depth-metrics only) the same two with
+                   depth_metrics=True: two more launches after the depth loss; the feature's cost
+                   per batch is valstep_graph_depth - valstep_graph of the same series
 
 A block is `--block` calls, synchronised once at its end; its figure is ms per call.  Per
 setting: the median over blocks and their spread (min, max).  Launches are not traced.  The
@@ -20,7 +23,7 @@ times the kernels behind each, LAUNCHES below); the torch kernels ControlValLoss
 launch are an ASSUMED count read off loss/control_loss.py; the result line says so
 (launch_count_basis).
 
-    python scripts/bench_val.py [--blocks 12] [--block 10] [--json out.json]
+    python scripts/bench_val.py [--blocks 12] [--block 10] [--depth-metrics] [--json out.json]
 """
 import argparse
 import json
@@ -35,7 +38,8 @@ import torch  # noqa: E402
 
 # kernel launches behind one call of a metric entry point (csrc/val.hip, csrc/loss.hip)
 LAUNCHES = {"e2ep_control_val_fwd": 2, "e2ep_seg_confusion": 2, "e2ep_val_accumulate": 1,
-            "e2ep_seg_ce_fwd": 2, "e2ep_depth_bce_fwd": 2, "e2ep_depth_bce_fwd_f64": 2}
+            "e2ep_seg_ce_fwd": 2, "e2ep_depth_bce_fwd": 2, "e2ep_depth_bce_fwd_f64": 2,
+            "e2ep_depth_metrics": 2, "e2ep_depth_metrics_f64": 2}
 # ControlValLoss.forward as torch kernels, assumed one per op: 3 softmax, 2 argmax, 1 float
 # cast, acc: gt, 2 x (div, sub), neg, where; steer: div, sub; 2 x smooth_l1 (+ 2 reshape
 # copies of the strided argmax results); 2 partial sums, stack, CE on the transposed pair
@@ -49,6 +53,8 @@ def main():
     ap.add_argument("--blocks", type=int, default=12, help="timed blocks per setting")
     ap.add_argument("--block", type=int, default=10, help="calls per block")
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--depth-metrics", action="store_true",
+                    help="add the two ValStep settings with depth_metrics=True")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     from e2ep_amd import _lib, synthetic
@@ -72,6 +78,11 @@ def main():
 
     calls = {"eager": eager, "eager2": eager, "valstep_eager": lambda: v_eager(),
              "valstep_graph": lambda: v_graph()}
+    if a.depth_metrics:
+        v_eager_d = ValStep(mod, data, noise=noise, graph=False, depth_metrics=True)
+        v_graph_d = ValStep(mod, data, noise=noise, graph=True, warmup=2, depth_metrics=True)
+        calls["valstep_eager_depth"] = lambda: v_eager_d()
+        calls["valstep_graph_depth"] = lambda: v_graph_d()
 
     def block(name):
         fn = calls[name]
@@ -86,6 +97,9 @@ def main():
         block(n)
     v_eager.reset()
     v_graph.reset()
+    if a.depth_metrics:
+        v_eager_d.reset()
+        v_graph_d.reset()
     times = {n: [] for n in order}
     for r in range(a.blocks):
         for n in order[r % len(order):] + order[:r % len(order)]:  # rotate who goes first
@@ -127,6 +141,28 @@ def main():
     res["val_loss_mean"] = [r_e["val_loss"], r_g["val_loss"]]
     res["eager_val_loss"] = float(mod.logged["val_loss"])
     res["seg_miou"] = r_g["seg_miou"]
+    if a.depth_metrics:
+        count[0] = 0
+        _lib.call = counted
+        try:
+            v_eager_d()
+        finally:
+            _lib.call = orig
+        torch.cuda.synchronize()
+        res["valstep_depth_metric_launches_per_call"] = count[0]
+        res["depth_cost_graph_ms"] = round(res["valstep_graph_depth"]["median_ms"]
+                                           - res["valstep_graph"]["median_ms"], 4)
+        res["depth_cost_eager_ms"] = round(res["valstep_eager_depth"]["median_ms"]
+                                           - res["valstep_eager"]["median_ms"], 4)
+        res["valstep_graph_spread_ms"] = round(res["valstep_graph"]["max_ms"]
+                                               - res["valstep_graph"]["min_ms"], 4)
+        res["valstep_graph_depth_spread_ms"] = round(res["valstep_graph_depth"]["max_ms"]
+                                                     - res["valstep_graph_depth"]["min_ms"], 4)
+        r_d = v_graph_d.result()
+        res["val_loss_mean_depth"] = [v_eager_d.result()["val_loss"], r_d["val_loss"]]
+        res["depth_metrics"] = {k: v for k, v in r_d.items()
+                                if k.startswith("depth_") and k != "depth_per_camera"}
+        res["depth_bin_acc_per_camera"] = r_d["depth_per_camera"]["depth_bin_acc"].tolist()
     print(json.dumps(res))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
