@@ -12,6 +12,12 @@
 // reads the coefficient and the flag there: one capturable chain, no host synchronisation, no
 // atomics, the same bits whatever the gradient source or its alignment.  k_grad_accum adds a
 // micro-step's gradients into the flat buffer (gradient accumulation).
+//
+// Optional (e2ep_adam_step_ema): an exponential moving average of the weights, a fourth flat
+// buffer in the parameter layout, updated by the Adam launch itself while the new weight is
+// still in a register: 9 x 4 bytes per weight instead of 7 x 4, no second pass.  k_flat_swap
+// exchanges the contents of two flat buffers (evaluate with the averaged weights: every
+// parameter keeps its address, so captured graphs see the swap).
 #include "common.h"
 
 namespace e2ep {
@@ -34,7 +40,18 @@ __global__ void k_adam_count(float *step) { step[0] += 1.f; }
 // The update of one chunk-table row {tensor, start element within tensor, length, unused}.
 // CLIP: the gradient is also multiplied by a clip coefficient read from device memory (after
 // grad_scale, before the weight decay), for the launch that follows k_gnorm_final.
-template <bool CLIP>
+// EMA: after an element's new p is known, ema = ema + ew * (p - ema), formed as ONE fp32 fused
+// multiply-add fmaf(ew, p - ema, ema) (the subtraction rounds, the multiply-add rounds once);
+// written as __fmaf_rn so that the vector path, its scalar tail and the unaligned-gradient
+// path give the same bits whatever the compiler's contraction setting.  A row whose tensor has
+// no gradient keeps p, m, v and `stepped` and still averages toward the unchanged p
+// (torch.optim.swa_utils.AveragedModel.update_parameters); with ema == p, as it is from
+// construction for a tensor that is never stepped, that is the identity (ew * 0 + ema).
+__device__ __forceinline__ float ema_upd(float ev, float pv, float ew) {
+  return __fmaf_rn(ew, pv - ev, ev);
+}
+
+template <bool CLIP, bool EMA = false>
 __device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
                                          const long long *__restrict__ offs,
                                          const long long *__restrict__ gptrs,
@@ -42,14 +59,37 @@ __device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
                                          float *__restrict__ m, float *__restrict__ v,
                                          const float *__restrict__ step,
                                          const double *__restrict__ lr, const AdamHyper &h,
-                                         float coef, int *__restrict__ stepped) {
+                                         float coef, int *__restrict__ stepped,
+                                         float *__restrict__ ema = nullptr, float ew = 0.f) {
   const int4 c = chunks[blockIdx.x];
   const long long off = offs[c.x] + c.y;
   // a parameter without a gradient this step is not stepped (as torch.optim.Adam); on the
   // flat (all-reduced) path the table still says which parameters had one, so the result
   // does not depend on the world size
   const float *gt = gptrs ? reinterpret_cast<const float *>(gptrs[c.x]) : nullptr;
-  if (gptrs && gt == nullptr) return;
+  if (gptrs && gt == nullptr) {  // block-uniform
+    if (EMA) {  // p and ema rows are 16-byte aligned by the layout
+      const float *pp = p + off;
+      float *ep = ema + off;
+#pragma unroll
+      for (int it = 0; it < ADAM_ITERS; ++it) {
+        const int i = (it * ADAM_THREADS + threadIdx.x) * ADAM_VEC;
+        if (i >= c.z) break;
+        if (i + ADAM_VEC <= c.z) {
+          const float4 P = *reinterpret_cast<const float4 *>(pp + i);
+          float4 E = *reinterpret_cast<const float4 *>(ep + i);
+          E.x = ema_upd(E.x, P.x, ew);
+          E.y = ema_upd(E.y, P.y, ew);
+          E.z = ema_upd(E.z, P.z, ew);
+          E.w = ema_upd(E.w, P.w, ew);
+          *reinterpret_cast<float4 *>(ep + i) = E;
+        } else {
+          for (int j = i; j < c.z; ++j) ep[j] = ema_upd(ep[j], pp[j], ew);
+        }
+      }
+    }
+    return;
+  }
   // per-tensor "stepped at least once" flag (torch.optim.Adam keeps state only for those)
   if (stepped && c.y == 0 && threadIdx.x == 0) stepped[c.x] = 1;
   const float *g = gflat ? gflat + off : gt + c.y;
@@ -62,6 +102,7 @@ __device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
   const float bc2s = (float)sqrt(bc2);
   const float w1 = h.w1, w2 = h.w2;
   float *pp = p + off, *mp = m + off, *vp = v + off;
+  float *ep = EMA ? ema + off : nullptr;
   const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;  // wave-uniform
   auto upd = [&](float &pv, float &mv, float &vv, float gv) {
     gv = gv * h.grad_scale;
@@ -82,6 +123,8 @@ __device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
         float4 M = *reinterpret_cast<const float4 *>(mp + i);
         float4 V = *reinterpret_cast<const float4 *>(vp + i);
         const float4 G = *reinterpret_cast<const float4 *>(g + i);
+        float4 E;
+        if (EMA) E = *reinterpret_cast<const float4 *>(ep + i);
         upd(P.x, M.x, V.x, G.x);
         upd(P.y, M.y, V.y, G.y);
         upd(P.z, M.z, V.z, G.z);
@@ -89,12 +132,25 @@ __device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
         *reinterpret_cast<float4 *>(pp + i) = P;
         *reinterpret_cast<float4 *>(mp + i) = M;
         *reinterpret_cast<float4 *>(vp + i) = V;
+        if (EMA) {
+          E.x = ema_upd(E.x, P.x, ew);
+          E.y = ema_upd(E.y, P.y, ew);
+          E.z = ema_upd(E.z, P.z, ew);
+          E.w = ema_upd(E.w, P.w, ew);
+          *reinterpret_cast<float4 *>(ep + i) = E;
+        }
       } else {
-        for (int j = i; j < c.z; ++j) upd(pp[j], mp[j], vp[j], g[j]);
+        for (int j = i; j < c.z; ++j) {
+          upd(pp[j], mp[j], vp[j], g[j]);
+          if (EMA) ep[j] = ema_upd(ep[j], pp[j], ew);
+        }
       }
     }
   } else {
-    for (int j = threadIdx.x; j < c.z; j += ADAM_THREADS) upd(pp[j], mp[j], vp[j], g[j]);
+    for (int j = threadIdx.x; j < c.z; j += ADAM_THREADS) {
+      upd(pp[j], mp[j], vp[j], g[j]);
+      if (EMA) ep[j] = ema_upd(ep[j], pp[j], ew);
+    }
   }
 }
 
@@ -199,6 +255,56 @@ __global__ void __launch_bounds__(ADAM_THREADS)
                 int *__restrict__ stepped) {
   if (skip[0] != 0) return;
   adam_row<true>(chunks, offs, gptrs, gflat, p, m, v, step, lr, h, coef[0], stepped);
+}
+
+// ---- EMA shadow weights (e2ep_adam_step_ema) and the buffer swap ----
+
+// the step counter and the EMA update counter move together; neither moves on a skipped step
+__global__ void k_adam_count_ema(float *step, long long *ema_updates,
+                                 const int *__restrict__ skip) {
+  if (skip && skip[0] != 0) return;
+  step[0] += 1.f;
+  ema_updates[0] += 1;
+}
+
+// k_adam / k_adam_clip with the EMA epilogue.  The averaging weight is evaluated in double,
+// like Adam's scalars: d_t = decay, or with warm-up min(decay, (1 + n) / (10 + n)) (timm's
+// ModelEmaV2 warm-up) with n = ema_updates[0] after the count launch (1 on the first update);
+// ew = (float)(1 - d_t).  coef / skip may be null (no clipping / no skip flag).
+template <bool CLIP>
+__global__ void __launch_bounds__(ADAM_THREADS)
+    k_adam_ema(const int4 *__restrict__ chunks, const long long *__restrict__ offs,
+               const long long *__restrict__ gptrs, const float *__restrict__ gflat,
+               float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
+               const float *__restrict__ step, const double *__restrict__ lr, AdamHyper h,
+               const float *__restrict__ coef, const int *__restrict__ skip,
+               int *__restrict__ stepped, float *__restrict__ ema,
+               const long long *__restrict__ ema_updates, double decay, int warmup) {
+  if (skip && skip[0] != 0) return;
+  double d = decay;
+  if (warmup) {
+    const double n = (double)ema_updates[0];
+    d = fmin(decay, (1.0 + n) / (10.0 + n));
+  }
+  const float ew = (float)(1.0 - d);
+  adam_row<CLIP, true>(chunks, offs, gptrs, gflat, p, m, v, step, lr, h, CLIP ? coef[0] : 1.f,
+                       stepped, ema, ew);
+}
+
+// a[i] <-> b[i] over n4 float4s: 16-byte accesses, grid-stride (the grid is capped, see
+// e2ep_flat_swap), each element read and written by one thread only
+constexpr int SWAP_THREADS = 256;
+constexpr int SWAP_MAX_BLOCKS = 2048;  // 256 CUs x 8 workgroups
+
+__global__ void __launch_bounds__(SWAP_THREADS)
+    k_flat_swap(float4 *__restrict__ a, float4 *__restrict__ b, long long n4) {
+  const long long stride = (long long)gridDim.x * SWAP_THREADS;
+  for (long long i = (long long)blockIdx.x * SWAP_THREADS + threadIdx.x; i < n4; i += stride) {
+    const float4 A = a[i];
+    const float4 B = b[i];
+    a[i] = B;
+    b[i] = A;
+  }
 }
 
 // gather per-tensor gradients into the flat (aligned, zero-padded) buffer for all-reduce
@@ -318,6 +424,49 @@ int e2ep_adam_step_clipped(const int *chunks, int n_chunks, const long long *off
                      reinterpret_cast<const int4 *>(chunks), offsets, grad_ptrs, grad_flat, param,
                      exp_avg, exp_avg_sq, step, lr, h, clip_coef, skip, stepped);
   return launch_status("e2ep_adam_step_clipped");
+}
+
+int e2ep_adam_step_ema(const int *chunks, int n_chunks, const long long *offsets,
+                       const long long *grad_ptrs, const float *grad_flat, float *param,
+                       float *exp_avg, float *exp_avg_sq, float *step, const double *lr,
+                       double beta1, double beta2, double eps, double weight_decay,
+                       float grad_scale, const float *clip_coef, const int *skip, int *stepped,
+                       float *ema, long long *ema_updates, double ema_decay, int ema_warmup,
+                       void *stream) {
+  E2EP_REQUIRE(n_chunks > 0 && chunks && offsets && param && exp_avg && exp_avg_sq && step && lr &&
+                   ema && ema_updates,
+               E2EP_EINVAL, "e2ep_adam_step_ema: null argument");
+  E2EP_REQUIRE(grad_ptrs || grad_flat, E2EP_EINVAL, "e2ep_adam_step_ema: no gradients");
+  E2EP_REQUIRE(ema_decay >= 0.0 && ema_decay < 1.0, E2EP_EINVAL,
+               "e2ep_adam_step_ema: ema_decay must be in [0, 1)");
+  E2EP_REQUIRE(ema != param && ema != exp_avg && ema != exp_avg_sq, E2EP_EINVAL,
+               "e2ep_adam_step_ema: ema aliases another buffer");
+  AdamHyper h{beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+              (float)(1.0 - beta2), (float)eps, (float)weight_decay, grad_scale};
+  hipLaunchKernelGGL(k_adam_count_ema, dim3(1), dim3(1), 0, as_stream(stream), step, ema_updates,
+                     skip);
+  auto kern = clip_coef ? k_adam_ema<true> : k_adam_ema<false>;
+  hipLaunchKernelGGL(kern, dim3(n_chunks), dim3(ADAM_THREADS), 0, as_stream(stream),
+                     reinterpret_cast<const int4 *>(chunks), offsets, grad_ptrs, grad_flat, param,
+                     exp_avg, exp_avg_sq, step, lr, h, clip_coef, skip, stepped, ema,
+                     static_cast<const long long *>(ema_updates), ema_decay, ema_warmup);
+  return launch_status("e2ep_adam_step_ema");
+}
+
+int e2ep_flat_swap(float *a, float *b, long long n, void *stream) {
+  E2EP_REQUIRE(a && b, E2EP_EINVAL, "e2ep_flat_swap: null argument");
+  E2EP_REQUIRE(n > 0 && n % 4 == 0, E2EP_EINVAL,
+               "e2ep_flat_swap: n must be a positive multiple of 4");
+  E2EP_REQUIRE(a != b, E2EP_EINVAL, "e2ep_flat_swap: a and b are the same buffer");
+  E2EP_REQUIRE(a + n <= b || b + n <= a, E2EP_EINVAL, "e2ep_flat_swap: a and b overlap");
+  E2EP_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0,
+               E2EP_EINVAL, "e2ep_flat_swap: buffers must be 16-byte aligned");
+  const long long n4 = n / 4;
+  const long long blocks = (n4 + SWAP_THREADS - 1) / SWAP_THREADS;
+  const int grid = (int)(blocks < SWAP_MAX_BLOCKS ? blocks : SWAP_MAX_BLOCKS);
+  hipLaunchKernelGGL(k_flat_swap, dim3(grid), dim3(SWAP_THREADS), 0, as_stream(stream),
+                     reinterpret_cast<float4 *>(a), reinterpret_cast<float4 *>(b), n4);
+  return launch_status("e2ep_flat_swap");
 }
 
 int e2ep_grad_accumulate(const int *chunks, int n_chunks, const long long *offsets,

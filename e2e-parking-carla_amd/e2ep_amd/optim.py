@@ -40,7 +40,32 @@ Optional, all off by default (step() then makes exactly the calls it always made
     step(flat, 1 / micro_steps, has_grad=union).
 The two settings are attributes and no optimizer state (state_dict() does not carry them); a
 captured step keeps the values it was captured with.
+
+Exponential moving average of the weights (ema_decay=, ema_warmup=; off by default, then
+nothing is allocated and step() makes the calls it always made).  `ema` is a fourth flat
+buffer in the parameter layout, initialised to the parameters; step() calls
+e2ep_adam_step_ema in place of either Adam entry point, whose update launch also forms
+ema += (1 - d_t) * (p_new - ema) while the new weight is in a register (9 x 4 bytes per weight
+instead of 7 x 4, no extra launch).  d_t = ema_decay, or with ema_warmup
+min(ema_decay, (1 + n) / (10 + n)) for the n-th update (timm's ModelEmaV2 warm-up); n lives in
+`ema_updates_dev` (int64, device), so a captured step warms up under replay.  A tensor without
+a gradient keeps its weights and still averages toward them
+(torch.optim.swa_utils.AveragedModel.update_parameters); a skipped step changes neither the
+average nor the counter.  Under data parallelism every rank computes the same average from
+the same weights: nothing is exchanged.
+`with opt.ema_weights():` evaluates with the averaged weights: ONE e2ep_flat_swap launch
+exchanges the contents of `flat` and `ema` (the live weights are parked in `ema`), the exit
+swaps back.  No parameter's address changes, so captured TrainStep / ValStep / AgentStep
+graphs see the averaged weights with nothing re-captured.  Swap once per validation epoch,
+around the whole loop over batches, not once per batch.  While the context is active the
+optimizer refuses to step, accumulate, reset or load the average.
+BatchNorm running statistics are module buffers, not parameters, and already moving
+averages: they are no part of FlatAdam and are neither averaged nor swapped.
+The average is no torch.optim.Adam state: state_dict() / load_state_dict() do not carry it
+(ema_state() / load_ema_state() do; checkpoint.py stores it next to the weights).
 """
+import contextlib
+
 import torch
 
 from . import _lib
@@ -50,7 +75,7 @@ _ALIGN = 4  # elements (16 bytes)
 
 class FlatAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         params = list(params)
         if not params:
             raise ValueError("FlatAdam: empty parameter list")
@@ -115,6 +140,93 @@ class FlatAdam(torch.optim.Optimizer):
         self._skip_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self._partials = torch.zeros(self.n_chunks, dtype=torch.float64, device=dev)
         self._has_i64 = torch.zeros(len(self.params), dtype=torch.int64, device=dev)
+        # weight averaging (module docstring): nothing is allocated while it is off
+        self.ema_decay, self.ema_warmup = None, False
+        self.ema = self.ema_updates_dev = None
+        self._ema_swapped = False
+        if ema_decay is not None:
+            self.enable_ema(ema_decay, ema_warmup)
+
+    # -- weight averaging ---------------------------------------------------------------------
+    def enable_ema(self, decay, warmup=False):
+        """Switch weight averaging on (or change its settings): 0 <= decay < 1.  The first call
+        allocates `ema` as a copy of the parameters and the update counter at 0; a later one
+        keeps both.  Outside graph capture and before the step is captured."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"FlatAdam: ema_decay must be in [0, 1), got {decay}")
+        self._ema_guard("enable_ema")
+        self.ema_decay, self.ema_warmup = decay, bool(warmup)
+        if self.ema is None:
+            self.ema = torch.empty_like(self.flat).copy_(self.flat)  # pads are zero, as flat's
+            self.ema_updates_dev = torch.zeros(1, dtype=torch.int64, device=self.flat.device)
+
+    def _ema_guard(self, what, need_ema=False):
+        if need_ema and self.ema is None:
+            raise _lib.E2EPError(f"FlatAdam.{what}: weight averaging is off (ema_decay=None)")
+        if self._ema_swapped:
+            raise _lib.E2EPError(f"FlatAdam.{what} inside ema_weights(): the parameters hold "
+                                 "the averaged weights")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.E2EPError(f"FlatAdam.{what} during stream capture")
+
+    def ema_param(self, i):
+        """The averaged values of parameter i (a view of `ema` shaped like it).  Inside
+        ema_weights() the buffers are exchanged: this is then the parked live parameter."""
+        if self.ema is None:
+            raise _lib.E2EPError("FlatAdam.ema_param: weight averaging is off (ema_decay=None)")
+        o, n = self.spans[i]
+        return self.ema[o:o + n].view_as(self.params[i])
+
+    def reset_ema(self):
+        """ema = the current parameters, update counter = 0.  Not during capture."""
+        self._ema_guard("reset_ema", need_ema=True)
+        self.ema.copy_(self.flat)
+        self.ema_updates_dev.zero_()
+
+    def ema_state(self):
+        """{"decay", "warmup", "num_updates", "flat": a clone of `ema`} (reading the counter
+        synchronises)."""
+        self._ema_guard("ema_state", need_ema=True)
+        return {"decay": float(self.ema_decay), "warmup": bool(self.ema_warmup),
+                "num_updates": int(self.ema_updates_dev.item()), "flat": self.ema.clone()}
+
+    def load_ema_state(self, state):
+        """Load what ema_state() returned (settings, counter and the averaged weights)."""
+        self._ema_guard("load_ema_state", need_ema=True)
+        flat = state["flat"]
+        if flat.numel() != self.numel:
+            raise ValueError(f"FlatAdam.load_ema_state: {flat.numel()} values for a layout of "
+                             f"{self.numel}")
+        decay = float(state["decay"])
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"FlatAdam: ema_decay must be in [0, 1), got {decay}")
+        self.ema_decay, self.ema_warmup = decay, bool(state["warmup"])
+        self.ema.copy_(flat.reshape(-1))
+        self.ema_updates_dev.fill_(int(state["num_updates"]))
+
+    def _swap(self):
+        _lib.call("e2ep_flat_swap", _lib.ptr(self.flat), _lib.ptr(self.ema), self.numel,
+                  _lib.stream())
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate with the averaged weights: one launch exchanges the contents of `flat` and
+        `ema` on entry and one exchanges them back on exit, on the current stream (module
+        docstring).  Does not nest; not during stream capture."""
+        self._ema_guard("ema_weights", need_ema=True)
+        self._swap()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap()
+            self._ema_swapped = False
+
+    @property
+    def ema_active(self):
+        """True inside ema_weights()."""
+        return self._ema_swapped
 
     # -- learning rate ------------------------------------------------------------------------
     @property
@@ -179,6 +291,8 @@ class FlatAdam(torch.optim.Optimizer):
         gradient, so `flat` needs no clearing), every later one adds (such a tensor adds
         nothing).  Pair it with has_grad(out, union=not first), then
         step(flat, 1 / micro_steps, has_grad=out)."""
+        if self._ema_swapped:
+            self._ema_guard("accumulate_grads")
         if first:
             self.gather_grads(flat)
             return
@@ -212,6 +326,8 @@ class FlatAdam(torch.optim.Optimizer):
         With max_grad_norm or skip_nonfinite set, the norm of the scaled gradient is taken
         first and the update reads the clip coefficient and the skip flag from device memory
         (module docstring); the norm is over the tensors that are stepped."""
+        if self._ema_swapped:
+            self._ema_guard("step")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -223,7 +339,11 @@ class FlatAdam(torch.optim.Optimizer):
         table = _lib.ptr(has_grad if (has_grad is not None and grad_flat is not None)
                          else self._gtab)
         gflat = _lib.ptr(grad_flat) if grad_flat is not None else None
-        if self.max_grad_norm is None and not self.skip_nonfinite:
+        plain = self.max_grad_norm is None and not self.skip_nonfinite
+        if plain and self.ema is not None:
+            self._step_ema(table, gflat, grad_scale, None, None)
+            return loss
+        if plain:
             _lib.call("e2ep_adam_step", _lib.ptr(self.chunks), self.n_chunks,
                       _lib.ptr(self.offsets), table, gflat,
                       _lib.ptr(self.flat), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
@@ -242,6 +362,9 @@ class FlatAdam(torch.optim.Optimizer):
                   float(grad_scale), max_norm, int(self.skip_nonfinite),
                   _lib.ptr(self.grad_norm_dev), _lib.ptr(self.clip_coef_dev),
                   _lib.ptr(self._skip_dev), _lib.ptr(self.skipped_dev), _lib.stream())
+        if self.ema is not None:
+            self._step_ema(table, gflat, grad_scale, self.clip_coef_dev, self._skip_dev)
+            return loss
         _lib.call("e2ep_adam_step_clipped", _lib.ptr(self.chunks), self.n_chunks,
                   _lib.ptr(self.offsets), table, gflat,
                   _lib.ptr(self.flat), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
@@ -250,6 +373,17 @@ class FlatAdam(torch.optim.Optimizer):
                   _lib.ptr(self.clip_coef_dev), _lib.ptr(self._skip_dev),
                   _lib.ptr(self.stepped), _lib.stream())
         return loss
+
+    def _step_ema(self, table, gflat, grad_scale, coef, skip):
+        b1, b2 = self.betas
+        _lib.call("e2ep_adam_step_ema", _lib.ptr(self.chunks), self.n_chunks,
+                  _lib.ptr(self.offsets), table, gflat,
+                  _lib.ptr(self.flat), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                  _lib.ptr(self.step_count), _lib.ptr(self.lr_dev), float(b1), float(b2),
+                  float(self.eps), float(self.weight_decay), float(grad_scale),
+                  _lib.ptr(coef), _lib.ptr(skip), _lib.ptr(self.stepped),
+                  _lib.ptr(self.ema), _lib.ptr(self.ema_updates_dev), float(self.ema_decay),
+                  int(self.ema_warmup), _lib.stream())
 
     # -- torch.optim.Adam-format state --------------------------------------------------------
     def state_dict(self):

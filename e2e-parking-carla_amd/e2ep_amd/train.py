@@ -206,11 +206,23 @@ class TrainStep:
     launch.  With accumulate > 1 and data parallelism the exchange happens once per cycle, on
     the accumulated buffer, over the non-overlapped, non-segmented path: `segmented` is False
     and `buckets` is None whatever `segment` / `overlap` say.  `grad_norm` is the device
-    scalar holding the last update's norm before clipping."""
+    scalar holding the last update's norm before clipping.
+    ema_decay / ema_warmup (FlatAdam's weight averaging, optim.py) follow the same precedence:
+    the argument, then module.cfg.ema_decay / ema_warmup, then what a passed-in FlatAdam has;
+    they are switched on in the optimizer before the warm-up steps and the capture, and need a
+    FlatAdam.  The average lives in _update, so it moves once per update: the constructor's
+    warm-up steps are real steps and count, and with accumulate = A it moves on every A-th
+    call.  To validate with the averaged weights wrap the whole loop, one swap per epoch:
+        with step.opt.ema_weights():
+            for b in loader:
+                val(b)
+    Captured ValStep / AgentStep graphs on the same module see the swap as they are; calling
+    the TrainStep itself inside the context raises."""
 
     def __init__(self, module, batch, lr=1e-4, weight_decay=1e-4, world=1, graph=True,
                  warmup=3, optimizer=None, bucket_mb=BUCKET_MB, overlap=None, ddp=None,
-                 segment=True, max_grad_norm=None, skip_nonfinite=None, accumulate=None):
+                 segment=True, max_grad_norm=None, skip_nonfinite=None, accumulate=None,
+                 ema_decay=None, ema_warmup=None):
         self.module = module
         self.batch = batch
         self.world = world
@@ -235,14 +247,27 @@ class TrainStep:
         self.accumulate = 1 if accumulate is None else int(accumulate)
         if self.accumulate < 1:
             raise ValueError(f"TrainStep: accumulate must be >= 1, got {accumulate}")
+        # weight averaging: the same precedence (ema_decay=None cannot switch off what the
+        # config or the optimizer carries)
+        if ema_decay is None:
+            ema_decay = getattr(cfg, "ema_decay", None)
+        warm_given = ema_warmup is not None
+        if not warm_given:
+            ema_warmup = getattr(cfg, "ema_warmup", None)
         if isinstance(self.opt, FlatAdam):
             if max_grad_norm is not None:
                 self.opt.max_grad_norm = float(max_grad_norm)
             if skip_given or skip_nonfinite:
                 self.opt.skip_nonfinite = bool(skip_nonfinite)
+            decay = self.opt.ema_decay if ema_decay is None else float(ema_decay)
+            warm = bool(ema_warmup) if (warm_given or ema_warmup) else self.opt.ema_warmup
+            if decay is not None and (decay, warm) != (self.opt.ema_decay, self.opt.ema_warmup):
+                self.opt.enable_ema(decay, warm)  # before the warm-up steps and the capture
         elif max_grad_norm is not None or skip_nonfinite or self.accumulate > 1:
             raise ValueError("TrainStep: max_grad_norm, skip_nonfinite and accumulate need a "
                              "FlatAdam optimizer")
+        elif ema_decay is not None:
+            raise ValueError("TrainStep: ema_decay needs a FlatAdam optimizer")
         self._micro = 0  # position in the accumulation cycle
         dev = self.params[0].device
         flat = self.ddp or self.accumulate > 1
@@ -540,6 +565,9 @@ class TrainStep:
         """One micro-step (with accumulate == 1: one training step); `batch` (optional) is
         copied into the captured input buffers.  Returns this micro-batch's loss; every
         `accumulate`-th call also runs the exchange and the update."""
+        if getattr(self.opt, "ema_active", False):
+            raise _lib.E2EPError("TrainStep called inside FlatAdam.ema_weights(): the parameters "
+                                 "hold the averaged weights")
         if batch is not None:
             if self.graph and _rig_key(batch) != self._rig:
                 raise _lib.E2EPError(

@@ -7,6 +7,8 @@ Optional MI355X keys (absent from reference configs, defaults shown):
   gradient_clip_val: None       global gradient-norm clipping (Lightning's Trainer argument)
   accumulate_grad_batches: 1    micro-batches per optimizer update (Lightning's Trainer argument)
   skip_nonfinite_steps: False   leave out an update whose gradient norm is Inf or NaN
+  ema_decay: None               exponential moving average of the weights (0 <= decay < 1)
+  ema_warmup: False             timm's warm-up of that decay: min(decay, (1 + n) / (10 + n))
 """
 import os
 from datetime import datetime
@@ -33,6 +35,8 @@ class Configuration:
     gradient_clip_val = None
     accumulate_grad_batches = 1
     skip_nonfinite_steps = False
+    ema_decay = None
+    ema_warmup = False
 
 
 for _k in _KEYS:
@@ -53,6 +57,9 @@ def get_cfg(cfg_yaml: dict) -> Configuration:
     cfg.gradient_clip_val = None if clip is None else float(clip)
     cfg.accumulate_grad_batches = int(section.get("accumulate_grad_batches", 1))
     cfg.skip_nonfinite_steps = bool(section.get("skip_nonfinite_steps", False))
+    ema = section.get("ema_decay")
+    cfg.ema_decay = None if ema is None else float(ema)
+    cfg.ema_warmup = bool(section.get("ema_warmup", False))
     return cfg
 
 

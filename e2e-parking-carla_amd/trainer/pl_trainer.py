@@ -94,7 +94,9 @@ class ParkingTrainingModule(_Base):
             from e2ep_amd.optim import FlatAdam
             opt = FlatAdam(params, lr=self.cfg.learning_rate, weight_decay=self.cfg.weight_decay,
                            max_grad_norm=getattr(self.cfg, "gradient_clip_val", None),
-                           skip_nonfinite=getattr(self.cfg, "skip_nonfinite_steps", False))
+                           skip_nonfinite=getattr(self.cfg, "skip_nonfinite_steps", False),
+                           ema_decay=getattr(self.cfg, "ema_decay", None),
+                           ema_warmup=getattr(self.cfg, "ema_warmup", False))
         else:
             opt = torch.optim.Adam(params, lr=self.cfg.learning_rate,
                                    weight_decay=self.cfg.weight_decay)

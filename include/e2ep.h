@@ -783,6 +783,30 @@ int e2ep_adam_step_clipped(const int *chunks, int n_chunks, const long long *off
                            int *stepped, void *stream);
 int e2ep_grad_accumulate(const int *chunks, int n_chunks, const long long *offsets,
                          const long long *grad_ptrs, float *grad_flat, void *stream);
+/* Exponential moving average of the weights (torch.optim.swa_utils.AveragedModel, timm's
+ * ModelEmaV2), kept in a fourth flat buffer `ema` of the parameter layout and updated by the
+ * Adam launch itself.
+ *  - e2ep_adam_step_ema: e2ep_adam_step_clipped's arguments and contract, with clip_coef and
+ *    skip each allowed to be null (both null: e2ep_adam_step's update), plus the average.  One
+ *    count launch (step[0] += 1 and ema_updates[0] += 1, neither when skip[0] is set) and one
+ *    update launch.  After an element's new p is computed: ema = fmaf(w, p - ema, ema) in fp32,
+ *    w = (float)(1 - d_t), d_t = ema_decay, or with ema_warmup != 0
+ *    min(ema_decay, (1 + n) / (10 + n)), n = ema_updates[0] after the increment (1 on the first
+ *    update), evaluated in double.  0 <= ema_decay < 1.  A tensor without a gradient this step
+ *    keeps p, moments and `stepped`, and its average still moves toward the unchanged p (the
+ *    identity while ema == p).  When skip[0] is set the call changes nothing, ema and
+ *    ema_updates included.  The result does not depend on the gradient source or alignment.
+ *  - e2ep_flat_swap: exchanges the contents of a[0..n) and b[0..n) in place (16-byte
+ *    accesses; a and b 16-byte aligned).  n must be a positive multiple of 4 and the buffers
+ *    must not be the same or overlap: E2EP_EINVAL otherwise. */
+int e2ep_adam_step_ema(const int *chunks, int n_chunks, const long long *offsets,
+                       const long long *grad_ptrs, const float *grad_flat, float *param,
+                       float *exp_avg, float *exp_avg_sq, float *step, const double *lr,
+                       double beta1, double beta2, double eps, double weight_decay,
+                       float grad_scale, const float *clip_coef, const int *skip, int *stepped,
+                       float *ema, long long *ema_updates, double ema_decay, int ema_warmup,
+                       void *stream);
+int e2ep_flat_swap(float *a, float *b, long long n, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Training losses (fp32; fixed-order reductions; every scalar stays on the device):
