@@ -18,6 +18,14 @@
 // still in a register: 9 x 4 bytes per weight instead of 7 x 4, no second pass.  k_flat_swap
 // exchanges the contents of two flat buffers (evaluate with the averaged weights: every
 // parameter keeps its address, so captured graphs see the swap).
+//
+// Optional (e2ep_adam_step_groups): parameter groups.  The chunk-table row's fourth int is its
+// tensor's group; the launch reads that group's learning rate, weight decay and flags (bit 0:
+// decoupled, AdamW's p *= 1 - lr * wd in place of the L2 term g += wd * p) from three device
+// tables.  Still one launch and 7 x 4 bytes per weight (9 x 4 with the average); the gradient
+// norm, the clip coefficient, the step counter and the average stay global.  k_adam_groups is
+// adam_row with GROUPS set: the same expressions in the same order, so a grouped step gives the
+// bits of the ungrouped one where the hyper-parameters agree.
 #include "common.h"
 
 namespace e2ep {
@@ -37,7 +45,10 @@ constexpr int ADAM_ITERS = 4;
 
 __global__ void k_adam_count(float *step) { step[0] += 1.f; }
 
-// The update of one chunk-table row {tensor, start element within tensor, length, unused}.
+// The update of one chunk-table row {tensor, start element within tensor, length, group}.
+// GROUPS: the row's learning rate, weight decay and flags come from the group tables at c.w
+// (block-uniform); a row whose group is outside [0, n_groups) is left untouched and never
+// indexes them.  Without GROUPS c.w is not read: lr[0] and h.wd hold for every row.
 // CLIP: the gradient is also multiplied by a clip coefficient read from device memory (after
 // grad_scale, before the weight decay), for the launch that follows k_gnorm_final.
 // EMA: after an element's new p is known, ema = ema + ew * (p - ema), formed as ONE fp32 fused
@@ -51,7 +62,7 @@ __device__ __forceinline__ float ema_upd(float ev, float pv, float ew) {
   return __fmaf_rn(ew, pv - ev, ev);
 }
 
-template <bool CLIP, bool EMA = false>
+template <bool CLIP, bool EMA = false, bool GROUPS = false>
 __device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
                                          const long long *__restrict__ offs,
                                          const long long *__restrict__ gptrs,
@@ -60,8 +71,12 @@ __device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
                                          const float *__restrict__ step,
                                          const double *__restrict__ lr, const AdamHyper &h,
                                          float coef, int *__restrict__ stepped,
-                                         float *__restrict__ ema = nullptr, float ew = 0.f) {
+                                         float *__restrict__ ema = nullptr, float ew = 0.f,
+                                         const double *__restrict__ group_wd = nullptr,
+                                         const int *__restrict__ group_flags = nullptr,
+                                         int n_groups = 0) {
   const int4 c = chunks[blockIdx.x];
+  if (GROUPS && (unsigned)c.w >= (unsigned)n_groups) return;  // block-uniform
   const long long off = offs[c.x] + c.y;
   // a parameter without a gradient this step is not stepped (as torch.optim.Adam); on the
   // flat (all-reduced) path the table still says which parameters had one, so the result
@@ -98,16 +113,23 @@ __device__ __forceinline__ void adam_row(const int4 *__restrict__ chunks,
   const double t = (double)step[0];
   const double bc1 = 1.0 - pow(h.beta1, t);
   const double bc2 = 1.0 - pow(h.beta2, t);
-  const float step_size = (float)(lr[0] / bc1);
+  const double lrv = GROUPS ? lr[c.w] : lr[0];
+  const float step_size = (float)(lrv / bc1);
+  // L2 (torch.optim.Adam): g += wd * p.  Decoupled (AdamW): p *= 1 - lr * wd first, the
+  // product and the difference in double as torch forms them on the host, and no L2 term.
+  const bool decoupled = GROUPS && (group_flags[c.w] & 1) != 0;
+  const float wd = GROUPS ? (float)group_wd[c.w] : h.wd;
+  const float keep = decoupled ? (float)(1.0 - lrv * group_wd[c.w]) : 1.f;
   const float bc2s = (float)sqrt(bc2);
   const float w1 = h.w1, w2 = h.w2;
   float *pp = p + off, *mp = m + off, *vp = v + off;
   float *ep = EMA ? ema + off : nullptr;
   const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;  // wave-uniform
   auto upd = [&](float &pv, float &mv, float &vv, float gv) {
+    if (GROUPS && decoupled) pv = pv * keep;
     gv = gv * h.grad_scale;
     if (CLIP) gv = gv * coef;  // clip_grad_norm_: g.mul_(clip_coef), then Adam's g + wd * p
-    gv = gv + h.wd * pv;
+    if (!(GROUPS && decoupled)) gv = gv + wd * pv;
     mv = mv + w1 * (gv - mv);  // exp_avg.lerp_(grad, 1 - beta1)
     vv = vv * h.b2f + w2 * gv * gv;
     const float den = sqrtf(vv) / bc2s + h.eps;
@@ -291,6 +313,36 @@ __global__ void __launch_bounds__(ADAM_THREADS)
                        stepped, ema, ew);
 }
 
+// ---- parameter groups (e2ep_adam_step_groups) ----
+
+// k_adam / k_adam_clip / k_adam_ema in one: coef (CLIP), skip and ema (EMA) may be null.  `lr`
+// is the per-group table here.
+template <bool CLIP, bool EMA>
+__global__ void __launch_bounds__(ADAM_THREADS)
+    k_adam_groups(const int4 *__restrict__ chunks, const long long *__restrict__ offs,
+                  const long long *__restrict__ gptrs, const float *__restrict__ gflat,
+                  float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
+                  const float *__restrict__ step, const double *__restrict__ group_lr,
+                  const double *__restrict__ group_wd, const int *__restrict__ group_flags,
+                  int n_groups, AdamHyper h, const float *__restrict__ coef,
+                  const int *__restrict__ skip, int *__restrict__ stepped,
+                  float *__restrict__ ema, const long long *__restrict__ ema_updates,
+                  double decay, int warmup) {
+  if (skip && skip[0] != 0) return;
+  float ew = 0.f;
+  if (EMA) {
+    double d = decay;
+    if (warmup) {
+      const double n = (double)ema_updates[0];
+      d = fmin(decay, (1.0 + n) / (10.0 + n));
+    }
+    ew = (float)(1.0 - d);
+  }
+  adam_row<CLIP, EMA, true>(chunks, offs, gptrs, gflat, p, m, v, step, group_lr, h,
+                            CLIP ? coef[0] : 1.f, stepped, ema, ew, group_wd, group_flags,
+                            n_groups);
+}
+
 // a[i] <-> b[i] over n4 float4s: 16-byte accesses, grid-stride (the grid is capped, see
 // e2ep_flat_swap), each element read and written by one thread only
 constexpr int SWAP_THREADS = 256;
@@ -451,6 +503,48 @@ int e2ep_adam_step_ema(const int *chunks, int n_chunks, const long long *offsets
                      exp_avg, exp_avg_sq, step, lr, h, clip_coef, skip, stepped, ema,
                      static_cast<const long long *>(ema_updates), ema_decay, ema_warmup);
   return launch_status("e2ep_adam_step_ema");
+}
+
+int e2ep_adam_step_groups(const int *chunks, int n_chunks, const long long *offsets,
+                          const long long *grad_ptrs, const float *grad_flat, float *param,
+                          float *exp_avg, float *exp_avg_sq, float *step, const double *group_lr,
+                          const double *group_wd, const int *group_flags, int n_groups,
+                          double beta1, double beta2, double eps, float grad_scale,
+                          const float *clip_coef, const int *skip, int *stepped, float *ema,
+                          long long *ema_updates, double ema_decay, int ema_warmup,
+                          void *stream) {
+  E2EP_REQUIRE(n_chunks > 0 && chunks && offsets && param && exp_avg && exp_avg_sq && step,
+               E2EP_EINVAL, "e2ep_adam_step_groups: null argument");
+  E2EP_REQUIRE(grad_ptrs || grad_flat, E2EP_EINVAL, "e2ep_adam_step_groups: no gradients");
+  E2EP_REQUIRE(n_groups >= 1, E2EP_EINVAL, "e2ep_adam_step_groups: n_groups must be >= 1");
+  E2EP_REQUIRE(group_lr && group_wd && group_flags, E2EP_EINVAL,
+               "e2ep_adam_step_groups: null group table");
+  E2EP_REQUIRE((ema == nullptr) == (ema_updates == nullptr), E2EP_EINVAL,
+               "e2ep_adam_step_groups: ema and ema_updates go together");
+  if (ema) {
+    E2EP_REQUIRE(ema_decay >= 0.0 && ema_decay < 1.0, E2EP_EINVAL,
+                 "e2ep_adam_step_groups: ema_decay must be in [0, 1)");
+    E2EP_REQUIRE(ema != param && ema != exp_avg && ema != exp_avg_sq, E2EP_EINVAL,
+                 "e2ep_adam_step_groups: ema aliases another buffer");
+  }
+  // the weight decay is per group: AdamHyper's wd is not read by the grouped kernel
+  AdamHyper h{beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+              (float)(1.0 - beta2), (float)eps, 0.f, grad_scale};
+  if (ema)
+    hipLaunchKernelGGL(k_adam_count_ema, dim3(1), dim3(1), 0, as_stream(stream), step,
+                       ema_updates, skip);
+  else if (skip)
+    hipLaunchKernelGGL(k_adam_count_unless, dim3(1), dim3(1), 0, as_stream(stream), step, skip);
+  else
+    hipLaunchKernelGGL(k_adam_count, dim3(1), dim3(1), 0, as_stream(stream), step);
+  auto kern = ema ? (clip_coef ? k_adam_groups<true, true> : k_adam_groups<false, true>)
+                  : (clip_coef ? k_adam_groups<true, false> : k_adam_groups<false, false>);
+  hipLaunchKernelGGL(kern, dim3(n_chunks), dim3(ADAM_THREADS), 0, as_stream(stream),
+                     reinterpret_cast<const int4 *>(chunks), offsets, grad_ptrs, grad_flat, param,
+                     exp_avg, exp_avg_sq, step, group_lr, group_wd, group_flags, n_groups, h,
+                     clip_coef, skip, stepped, ema, static_cast<const long long *>(ema_updates),
+                     ema_decay, ema_warmup);
+  return launch_status("e2ep_adam_step_groups");
 }
 
 int e2ep_flat_swap(float *a, float *b, long long n, void *stream) {

@@ -11,15 +11,39 @@ autograd hands its result over without an accumulate).  For data parallelism the
 gradients are gathered into a flat buffer of the same layout by one more launch, and
 that buffer is what RCCL all-reduces.
 
-FlatAdam is a torch.optim.Optimizer with one param group, so the reference's
-CosineAnnealingLR (trainer/pl_trainer.py:120) binds to it unchanged.  The learning rate the
-kernel uses lives in a device fp64 scalar: step() (eager) and TrainStep (before each graph
-replay) copy param_groups[0]['lr'] into it when the scheduler has changed it, so a captured
-step follows the schedule.  betas / eps / weight_decay are fixed at construction (the
-reference never changes them).
+FlatAdam is a torch.optim.Optimizer, so the reference's CosineAnnealingLR
+(trainer/pl_trainer.py:120) binds to it unchanged.  The learning rates the kernel uses live
+in a device fp64 array `lr_dev`, one value per parameter group: step() (eager) and TrainStep
+(before each graph replay) copy every param_groups[k]['lr'] into it when the scheduler has
+changed any of them (sync_lr), so a captured step follows the schedule.  betas / eps /
+weight_decay are fixed at construction (the reference never changes them).
+
+Parameter groups.  `params` is a parameter list (one group) or a list of torch-style group
+dicts with the per-group keys `lr`, `weight_decay` and `decoupled_weight_decay` (torch 2.10's
+names; the constructor's arguments are the defaults; `name` and other keys are kept); betas
+and eps are shared (a group that overrides them: ValueError).  decoupled_weight_decay is
+AdamW's p *= 1 - lr * wd in place of the L2 term g += wd * p.  The chunk table's fourth int
+per row is the tensor's group, and `wd_dev` (fp64) / `flags_dev` (int32; bit 0: decoupled),
+written at construction and by load_state_dict, hold the other per-group values: still ONE
+update launch (e2ep_adam_step_groups), the same 7 x 4 bytes per weight; the gradient norm, the
+clip coefficient, the step counter, `stepped` and the average are global.  `order=` (a
+sequence of all the parameters; default: the groups concatenated) fixes the flat layout and
+with it the meaning of the indices in `params`, `spans`, `chunk_rows`, `group_of` and
+ema_param(i): with order= the module's parameter order, TrainStep, the gradient buckets, the
+segmented exchange and the checkpoint's "ema" entry see the layout they see without groups.
+A parameter in two groups, or an `order` that is not the groups' set of parameters, is a
+ValueError, and so is add_param_group (the layout is fixed).  `lr` means group 0.  One group
+without decoupled decay takes exactly the calls it always took (e2ep_adam_step, _clipped or
+_ema); every other optimizer takes e2ep_adam_step_groups, whose result for groups with equal
+hyper-parameters is bit for bit the ungrouped one.
+parameter_groups(module, ...) builds the usual fine-tuning recipe: a lower learning rate for
+the pretrained cam_encoder.backbone, no decay on norm scales, biases and pos_embed.
 
 state_dict() / load_state_dict() use torch.optim.Adam's format, so checkpoints move
-between this optimizer and the reference's.
+between this optimizer and the reference's: one entry per group, parameter indices in
+torch's convention (the groups concatenated), mapped through the layout permutation
+(layout_to_torch).  A torch.optim.Adam built with the same groups loads a FlatAdam state and
+the other way round.
 
 Optional, all off by default (step() then makes exactly the calls it always made):
   * max_grad_norm: global gradient-norm clipping, torch.nn.utils.clip_grad_norm_'s formula
@@ -73,24 +97,100 @@ from . import _lib
 _ALIGN = 4  # elements (16 bytes)
 
 
+def layout_to_torch(groups):
+    """`groups`: per parameter group, the layout positions of its parameters.  Returns `t` with
+    t[layout position] = the parameter's index in torch.optim's state_dict() convention (the
+    groups concatenated).  Every position 0 .. n-1 must appear exactly once."""
+    cat = [i for g in groups for i in g]
+    if sorted(cat) != list(range(len(cat))):
+        raise ValueError("layout_to_torch: the groups are no partition of 0 .. n-1")
+    t = [0] * len(cat)
+    for k, i in enumerate(cat):
+        t[i] = k
+    return t
+
+
+def parameter_groups(module, lr, weight_decay, backbone_lr_scale=1.0, no_decay_norm_bias=False,
+                     decoupled=False):
+    """The fine-tuning recipe as parameter groups: -> (groups, order).  `order` is the module's
+    trainable parameters in module order (FlatAdam's order=, so TrainStep and the exchange see
+    the layout they see without groups).  The groups are the non-empty cells of
+      backbone (name contains `cam_encoder.backbone.`, lr * backbone_lr_scale) / rest, taken
+        only when backbone_lr_scale != 1;
+      decay / no_decay (p.ndim <= 1: norm scales and biases, or a name ending in `pos_embed`;
+        weight_decay 0), taken only with no_decay_norm_bias;
+    named backbone_decay, backbone_no_decay, rest_decay, rest_no_decay, each a dict
+    {"params", "lr", "weight_decay", "decoupled_weight_decay", "name"} that torch.optim.Adam
+    and FlatAdam both take.  With the default arguments there is one group (rest_decay: every
+    trainable parameter): build the plain one-group optimizer from `order` then."""
+    named = [(n, p) for n, p in module.named_parameters() if p.requires_grad]
+    order = [p for _, p in named]
+    split_bb = float(backbone_lr_scale) != 1.0
+    cells = {}
+    for n, p in named:
+        bb = split_bb and "cam_encoder.backbone." in n
+        nd = bool(no_decay_norm_bias) and (p.ndim <= 1 or n.endswith("pos_embed"))
+        cells.setdefault((bb, nd), []).append(p)
+    groups = []
+    for bb in (True, False):
+        for nd in (False, True):
+            if (bb, nd) in cells:
+                groups.append({"params": cells[(bb, nd)],
+                               "lr": lr * backbone_lr_scale if bb else lr,
+                               "weight_decay": 0.0 if nd else weight_decay,
+                               "decoupled_weight_decay": bool(decoupled),
+                               "name": ("backbone" if bb else "rest") + ("_no_decay" if nd else "_decay")})
+    return groups, order
+
+
 class FlatAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False,
+                 decoupled_weight_decay=False, order=None):
         params = list(params)
         if not params:
             raise ValueError("FlatAdam: empty parameter list")
+        self._layout_fixed = False
         if isinstance(params[0], dict):
-            raise ValueError("FlatAdam: one parameter group only")
-        dev = params[0].device
+            groups = [dict(g, params=list(g["params"])) for g in params]
+            for g in groups:
+                if tuple(g.get("betas", betas)) != tuple(betas) or g.get("eps", eps) != eps:
+                    raise ValueError("FlatAdam: betas and eps are shared by all parameter groups")
+        else:
+            groups = [{"params": params}]
+        cat = [p for g in groups for p in g["params"]]
+        if not cat:
+            raise ValueError("FlatAdam: empty parameter list")
+        if len({id(p) for p in cat}) != len(cat):
+            raise ValueError("FlatAdam: a parameter appears in more than one parameter group")
+        if order is not None:
+            order = list(order)
+            if len(order) != len(cat) or {id(p) for p in order} != {id(p) for p in cat}:
+                raise ValueError("FlatAdam: `order` and the parameter groups do not hold the "
+                                 "same parameters")
+        dev = cat[0].device
         if dev.type != "cuda":
             raise _lib.E2EPError("FlatAdam runs on a HIP device only")
-        for p in params:
+        for p in cat:
             if p.dtype != torch.float32 or p.device != dev:
                 raise _lib.E2EPError("FlatAdam: parameters must be fp32 on one device")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps,
-                                      weight_decay=weight_decay))
-        self.params = self.param_groups[0]["params"]
-        self.betas, self.eps, self.weight_decay = tuple(betas), eps, weight_decay
+        super().__init__(groups, dict(lr=lr, betas=tuple(betas), eps=eps,
+                                      weight_decay=weight_decay,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
+        self._layout_fixed = True
+        # the flat layout: `order`, else the groups concatenated (one group: its own list)
+        self.params = (order if order is not None else
+                       self.param_groups[0]["params"] if len(groups) == 1 else cat)
+        pos = {id(p): i for i, p in enumerate(self.params)}
+        layout = [[pos[id(p)] for p in g["params"]] for g in self.param_groups]
+        self._torch_index = layout_to_torch(layout)
+        gid = [0] * len(self.params)
+        for k, g in enumerate(layout):
+            for i in g:
+                gid[i] = k
+        self.group_of = gid  # layout position -> parameter group
+        self.betas, self.eps = tuple(betas), eps
+        self.weight_decay = self.param_groups[0]["weight_decay"]
         lib = _lib.load()
         chunk = lib.e2ep_adam_chunk_elems()
         offs, rows, off = [], [], 0
@@ -98,7 +198,7 @@ class FlatAdam(torch.optim.Optimizer):
             offs.append(off)
             n = p.numel()
             for s in range(0, n, chunk):
-                rows.append((i, s, min(chunk, n - s), 0))
+                rows.append((i, s, min(chunk, n - s), gid[i]))
             off += (n + _ALIGN - 1) // _ALIGN * _ALIGN
         self.numel = off
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
@@ -128,8 +228,15 @@ class FlatAdam(torch.optim.Optimizer):
             n = (p.numel() + chunk - 1) // chunk
             self.chunk_rows.append((r, r + n))
             r += n
-        self.lr_dev = torch.full((1,), float(lr), dtype=torch.float64, device=dev)
-        self._lr_written = float(lr)
+        # one learning rate, weight decay and flag word (bit 0: decoupled) per group, in device
+        # memory: the grouped launch indexes them by the chunk row's group
+        lrs = [float(g["lr"]) for g in self.param_groups]
+        self.n_groups = len(lrs)
+        self.lr_dev = torch.tensor(lrs, dtype=torch.float64, device=dev)
+        self._lr_written = lrs
+        self.wd_dev = torch.zeros(self.n_groups, dtype=torch.float64, device=dev)
+        self.flags_dev = torch.zeros(self.n_groups, dtype=torch.int32, device=dev)
+        self._write_group_tables()
         # gradient-norm clipping / non-finite skip (module docstring): settings, the device
         # scalars the chain writes, and its workspace (one fp64 partial per chunk-table row)
         self.max_grad_norm = max_grad_norm
@@ -238,13 +345,34 @@ class FlatAdam(torch.optim.Optimizer):
         self.param_groups[0]["lr"] = v
 
     def sync_lr(self):
-        """Copy param_groups[0]['lr'] (an LR scheduler's output) into the device scalar the
-        Adam kernel reads, if it changed.  Not during capture: the kernel node reads the
-        scalar at replay time, the host writes it between replays."""
-        lr = float(self.param_groups[0]["lr"])
-        if lr != self._lr_written and not torch.cuda.is_current_stream_capturing():
-            self.lr_dev.fill_(lr)
-            self._lr_written = lr
+        """Copy every group's param_groups[k]['lr'] (an LR scheduler's output) into the device
+        array the Adam kernel reads, if any of them changed.  Not during capture: the kernel
+        node reads the array at replay time, the host writes it between replays."""
+        lrs = [float(g["lr"]) for g in self.param_groups]
+        if lrs != self._lr_written and not torch.cuda.is_current_stream_capturing():
+            if len(lrs) == 1:
+                self.lr_dev.fill_(lrs[0])
+            else:
+                self.lr_dev.copy_(torch.tensor(lrs, dtype=torch.float64))
+            self._lr_written = lrs
+
+    # -- parameter groups ---------------------------------------------------------------------
+    def add_param_group(self, param_group):
+        if self._layout_fixed:
+            raise ValueError("FlatAdam: the flat layout is fixed at construction; parameter "
+                             "groups cannot be added afterwards")
+        super().add_param_group(param_group)
+
+    def _write_group_tables(self):
+        """param_groups' weight_decay / decoupled_weight_decay -> wd_dev / flags_dev (at
+        construction and after load_state_dict; the learning rates go through sync_lr), and
+        which entry point step() takes: one L2 group keeps the three ungrouped ones."""
+        wds = [float(g["weight_decay"]) for g in self.param_groups]
+        dec = [bool(g.get("decoupled_weight_decay", False)) for g in self.param_groups]
+        self.wd_dev.copy_(torch.tensor(wds, dtype=torch.float64))
+        self.flags_dev.copy_(torch.tensor([int(d) for d in dec], dtype=torch.int32))
+        self.weight_decay = self.param_groups[0]["weight_decay"]
+        self.grouped = len(wds) > 1 or dec[0]
 
     # -- gradients --------------------------------------------------------------------------
     def zero_grad(self, set_to_none=True):
@@ -340,6 +468,9 @@ class FlatAdam(torch.optim.Optimizer):
                          else self._gtab)
         gflat = _lib.ptr(grad_flat) if grad_flat is not None else None
         plain = self.max_grad_norm is None and not self.skip_nonfinite
+        if plain and self.grouped:
+            self._step_groups(table, gflat, grad_scale, None, None)
+            return loss
         if plain and self.ema is not None:
             self._step_ema(table, gflat, grad_scale, None, None)
             return loss
@@ -362,6 +493,9 @@ class FlatAdam(torch.optim.Optimizer):
                   float(grad_scale), max_norm, int(self.skip_nonfinite),
                   _lib.ptr(self.grad_norm_dev), _lib.ptr(self.clip_coef_dev),
                   _lib.ptr(self._skip_dev), _lib.ptr(self.skipped_dev), _lib.stream())
+        if self.grouped:
+            self._step_groups(table, gflat, grad_scale, self.clip_coef_dev, self._skip_dev)
+            return loss
         if self.ema is not None:
             self._step_ema(table, gflat, grad_scale, self.clip_coef_dev, self._skip_dev)
             return loss
@@ -385,35 +519,75 @@ class FlatAdam(torch.optim.Optimizer):
                   _lib.ptr(self.ema), _lib.ptr(self.ema_updates_dev), float(self.ema_decay),
                   int(self.ema_warmup), _lib.stream())
 
+    def _step_groups(self, table, gflat, grad_scale, coef, skip):
+        """The grouped update: clipping (coef, skip) and the average are each on or null."""
+        b1, b2 = self.betas
+        ema = self.ema is not None
+        _lib.call("e2ep_adam_step_groups", _lib.ptr(self.chunks), self.n_chunks,
+                  _lib.ptr(self.offsets), table, gflat,
+                  _lib.ptr(self.flat), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                  _lib.ptr(self.step_count), _lib.ptr(self.lr_dev), _lib.ptr(self.wd_dev),
+                  _lib.ptr(self.flags_dev), self.n_groups, float(b1), float(b2),
+                  float(self.eps), float(grad_scale), _lib.ptr(coef), _lib.ptr(skip),
+                  _lib.ptr(self.stepped), _lib.ptr(self.ema), _lib.ptr(self.ema_updates_dev),
+                  float(self.ema_decay) if ema else 0.0, int(self.ema_warmup) if ema else 0,
+                  _lib.stream())
+
     # -- torch.optim.Adam-format state --------------------------------------------------------
     def state_dict(self):
+        """torch.optim.Adam's format: one entry per group, parameter indices in torch's
+        convention (the groups concatenated; layout_to_torch maps the layout positions).  One L2
+        group gives exactly the dict it always gave; otherwise every group also carries
+        `decoupled_weight_decay` (torch's key) and its `name` when it has one."""
         state = {}
         stepped = self.stepped.cpu().tolist()
         for i, (p, o) in enumerate(zip(self.params, self._offs_host)):
             if not stepped[i]:
                 continue
             n = p.numel()
-            state[i] = {"step": self.step_count[0].detach().cpu().clone(),
-                        "exp_avg": self.exp_avg[o:o + n].view_as(p).clone(),
-                        "exp_avg_sq": self.exp_avg_sq[o:o + n].view_as(p).clone()}
-        group = {"lr": float(self.lr), "betas": self.betas, "eps": self.eps,
-                 "weight_decay": self.weight_decay, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "params": list(range(len(self.params)))}
-        return {"state": state, "param_groups": [group]}
+            state[self._torch_index[i]] = {
+                "step": self.step_count[0].detach().cpu().clone(),
+                "exp_avg": self.exp_avg[o:o + n].view_as(p).clone(),
+                "exp_avg_sq": self.exp_avg_sq[o:o + n].view_as(p).clone()}
+        state = {k: state[k] for k in sorted(state)}
+        groups, first = [], 0
+        for g in self.param_groups:
+            n = len(g["params"])
+            group = {"lr": float(g["lr"]), "betas": self.betas, "eps": self.eps,
+                     "weight_decay": g["weight_decay"], "amsgrad": False, "maximize": False,
+                     "foreach": None, "capturable": False, "differentiable": False, "fused": None}
+            if self.grouped:
+                group["decoupled_weight_decay"] = bool(g.get("decoupled_weight_decay", False))
+                if "name" in g:
+                    group["name"] = g["name"]
+            if "initial_lr" in g and self.grouped:
+                group["initial_lr"] = g["initial_lr"]
+            group["params"] = list(range(first, first + n))
+            groups.append(group)
+            first += n
+        return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
-        g = sd["param_groups"][0]
-        self.betas, self.eps, self.weight_decay = tuple(g["betas"]), g["eps"], g["weight_decay"]
-        pg = self.param_groups[0]
-        pg.update(lr=g["lr"], betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
-        if "initial_lr" in g:
-            pg["initial_lr"] = g["initial_lr"]
+        saved = sd["param_groups"]
+        if len(saved) != len(self.param_groups) or any(
+                len(g["params"]) != len(pg["params"]) for g, pg in zip(saved, self.param_groups)):
+            raise ValueError("FlatAdam.load_state_dict: the state's parameter groups do not "
+                             "match the optimizer's")
+        if any(tuple(g["betas"]) != tuple(saved[0]["betas"]) or g["eps"] != saved[0]["eps"]
+               for g in saved):
+            raise ValueError("FlatAdam: betas and eps are shared by all parameter groups")
+        self.betas, self.eps = tuple(saved[0]["betas"]), saved[0]["eps"]
+        for g, pg in zip(saved, self.param_groups):
+            pg.update(lr=g["lr"], betas=self.betas, eps=self.eps, weight_decay=g["weight_decay"],
+                      decoupled_weight_decay=bool(g.get("decoupled_weight_decay", False)))
+            if "initial_lr" in g:
+                pg["initial_lr"] = g["initial_lr"]
+        self._write_group_tables()
         steps = set()
         with torch.no_grad():
             self.stepped.zero_()
             for i, (p, o) in enumerate(zip(self.params, self._offs_host)):
-                s = sd["state"].get(i)
+                s = sd["state"].get(self._torch_index[i])
                 if s is None:
                     continue
                 self.stepped[i] = 1

@@ -6,9 +6,16 @@ backward and the Adam update — is captured once into HIP graphs and replayed, 
 ~1,500 kernel launches of a step cost a few launches from the host.
 
 Optimizer: e2ep_amd.optim.FlatAdam (one fused launch over a flat parameter buffer; the
-gradients are read where autograd left them).  Its learning rate is a device scalar that
-__call__ refreshes from param_groups[0]['lr'] before each replay, so an LR scheduler
-(the reference's CosineAnnealingLR) acts on the captured step.
+gradients are read where autograd left them).  Its learning rates are a device array, one
+value per parameter group, that __call__ refreshes from param_groups[k]['lr'] before each
+replay, so an LR scheduler (the reference's CosineAnnealingLR) acts on the captured step.
+Parameter groups (optim.parameter_groups: a lower learning rate for the pretrained backbone,
+no weight decay on norm scales / biases / pos_embed, decoupled weight decay; module.cfg's
+backbone_lr_scale / no_decay_norm_bias / decoupled_weight_decay when TrainStep builds the
+optimizer) live in the optimizer's chunk table only: the flat layout stays the module's
+parameter order, so the gradient buffer, the buckets and the exchange do not see them.  A
+passed-in FlatAdam with more than one group must have that layout (order=; ValueError
+otherwise).
 
 Data parallelism (one process per GPU, RCCL over xGMI; DistributedDataParallel semantics
 without its module wrapper), one flat fp32 gradient buffer in FlatAdam's layout; the
@@ -67,7 +74,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, defer, graphs, segments
-from .optim import FlatAdam
+from .optim import FlatAdam, parameter_groups
 
 BUCKET_MB = 25.0  # DistributedDataParallel's default bucket_cap_mb
 
@@ -219,6 +226,20 @@ class TrainStep:
     Captured ValStep / AgentStep graphs on the same module see the swap as they are; calling
     the TrainStep itself inside the context raises."""
 
+    def _build_optimizer(self, module, lr, weight_decay):
+        """The optimizer TrainStep builds itself: optim.parameter_groups with module.cfg's
+        backbone_lr_scale / no_decay_norm_bias / decoupled_weight_decay; with all three at
+        their defaults the plain one-group FlatAdam."""
+        cfg = getattr(module, "cfg", None)
+        decoupled = bool(getattr(cfg, "decoupled_weight_decay", False))
+        groups, order = parameter_groups(
+            module, lr, weight_decay, float(getattr(cfg, "backbone_lr_scale", 1.0)),
+            bool(getattr(cfg, "no_decay_norm_bias", False)), decoupled)
+        if len(groups) == 1 and not decoupled:
+            return FlatAdam(self.params, lr=lr, weight_decay=weight_decay)
+        return FlatAdam(groups, lr=lr, weight_decay=weight_decay,
+                        decoupled_weight_decay=decoupled, order=order)
+
     def __init__(self, module, batch, lr=1e-4, weight_decay=1e-4, world=1, graph=True,
                  warmup=3, optimizer=None, bucket_mb=BUCKET_MB, overlap=None, ddp=None,
                  segment=True, max_grad_norm=None, skip_nonfinite=None, accumulate=None,
@@ -231,8 +252,14 @@ class TrainStep:
         self.ddp = world > 1 if ddp is None else bool(ddp)
         self.graph = graph
         self.params = [p for p in module.parameters() if p.requires_grad]
-        self.opt = optimizer if optimizer is not None else FlatAdam(
-            self.params, lr=lr, weight_decay=weight_decay)
+        self.opt = optimizer if optimizer is not None else self._build_optimizer(
+            module, lr, weight_decay)
+        if (isinstance(self.opt, FlatAdam) and len(self.opt.param_groups) > 1 and (
+                len(self.opt.params) != len(self.params)
+                or any(a is not b for a, b in zip(self.opt.params, self.params)))):
+            raise ValueError("TrainStep: a FlatAdam with parameter groups must be laid out in "
+                             "the module's parameter order (FlatAdam(groups, order=[p for p in "
+                             "module.parameters() if p.requires_grad]))")
         # clipping / non-finite skip / accumulation (class docstring): an explicit argument
         # wins, None falls back to module.cfg's Lightning-named keys, then to what the
         # optimizer already has

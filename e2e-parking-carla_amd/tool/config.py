@@ -9,6 +9,10 @@ Optional MI355X keys (absent from reference configs, defaults shown):
   skip_nonfinite_steps: False   leave out an update whose gradient norm is Inf or NaN
   ema_decay: None               exponential moving average of the weights (0 <= decay < 1)
   ema_warmup: False             timm's warm-up of that decay: min(decay, (1 + n) / (10 + n))
+  backbone_lr_scale: 1.0        learning rate of the pretrained cam_encoder.backbone, as a
+                                multiple of learning_rate (a parameter group of its own)
+  no_decay_norm_bias: False     no weight decay on norm scales, biases (ndim <= 1) and pos_embed
+  decoupled_weight_decay: False AdamW's p *= 1 - lr * wd in place of the L2 term
 """
 import os
 from datetime import datetime
@@ -37,6 +41,9 @@ class Configuration:
     skip_nonfinite_steps = False
     ema_decay = None
     ema_warmup = False
+    backbone_lr_scale = 1.0
+    no_decay_norm_bias = False
+    decoupled_weight_decay = False
 
 
 for _k in _KEYS:
@@ -60,6 +67,9 @@ def get_cfg(cfg_yaml: dict) -> Configuration:
     ema = section.get("ema_decay")
     cfg.ema_decay = None if ema is None else float(ema)
     cfg.ema_warmup = bool(section.get("ema_warmup", False))
+    cfg.backbone_lr_scale = float(section.get("backbone_lr_scale", 1.0))
+    cfg.no_decay_norm_bias = bool(section.get("no_decay_norm_bias", False))
+    cfg.decoupled_weight_decay = bool(section.get("decoupled_weight_decay", False))
     return cfg
 
 

@@ -88,18 +88,34 @@ class ParkingTrainingModule(_Base):
         (trainer/pl_trainer.py:116-121).  On a HIP device the optimizer is the fused flat Adam
         (same update; the schedule reaches its captured launches through a device LR scalar);
         parameters that never receive a gradient (bev_encoder.layer4, reference
-        model/bev_encoder.py:21) are not stepped by either optimizer."""
-        params = [p for p in self.parameters() if p.requires_grad]
+        model/bev_encoder.py:21) are not stepped by either optimizer.
+        cfg.backbone_lr_scale / no_decay_norm_bias / decoupled_weight_decay (tool/config.py) turn
+        the parameter list into optim.parameter_groups' groups, the same for both optimizers;
+        at their defaults there is one group and the optimizers are built as always."""
+        from e2ep_amd.optim import parameter_groups
+        decoupled = bool(getattr(self.cfg, "decoupled_weight_decay", False))
+        groups, params = parameter_groups(
+            self, self.cfg.learning_rate, self.cfg.weight_decay,
+            float(getattr(self.cfg, "backbone_lr_scale", 1.0)),
+            bool(getattr(self.cfg, "no_decay_norm_bias", False)), decoupled)
+        plain = len(groups) == 1 and not decoupled
         if params and params[0].is_cuda:
             from e2ep_amd.optim import FlatAdam
-            opt = FlatAdam(params, lr=self.cfg.learning_rate, weight_decay=self.cfg.weight_decay,
+            opt = FlatAdam(params if plain else groups, lr=self.cfg.learning_rate,
+                           weight_decay=self.cfg.weight_decay,
                            max_grad_norm=getattr(self.cfg, "gradient_clip_val", None),
                            skip_nonfinite=getattr(self.cfg, "skip_nonfinite_steps", False),
                            ema_decay=getattr(self.cfg, "ema_decay", None),
-                           ema_warmup=getattr(self.cfg, "ema_warmup", False))
-        else:
+                           ema_warmup=getattr(self.cfg, "ema_warmup", False),
+                           **({} if plain else dict(decoupled_weight_decay=decoupled,
+                                                    order=params)))
+        elif plain:
             opt = torch.optim.Adam(params, lr=self.cfg.learning_rate,
                                    weight_decay=self.cfg.weight_decay)
+        else:
+            opt = torch.optim.Adam(groups, lr=self.cfg.learning_rate,
+                                   weight_decay=self.cfg.weight_decay,
+                                   decoupled_weight_decay=decoupled)
         sched = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer=opt, T_max=self.cfg.epochs)
         return {"optimizer": opt, "lr_scheduler": sched}
 

@@ -807,6 +807,28 @@ int e2ep_adam_step_ema(const int *chunks, int n_chunks, const long long *offsets
                        float *ema, long long *ema_updates, double ema_decay, int ema_warmup,
                        void *stream);
 int e2ep_flat_swap(float *a, float *b, long long n, void *stream);
+/* Parameter groups (torch.optim's param_groups: a learning rate, a weight decay and the choice
+ * between L2 and decoupled weight decay per group), still in ONE update launch.
+ *  - e2ep_adam_step_groups: e2ep_adam_step_ema's arguments and contract with `lr` and
+ *    `weight_decay` replaced by three device tables of n_groups entries: group_lr and group_wd
+ *    (double) and group_flags (int; bit 0: decoupled weight decay).  clip_coef, skip, and ema
+ *    together with ema_updates may each be null: no clipping, no skip flag, no averaging.
+ *    Chunk-table row {tensor, start, length, group}: the row is updated with its group's
+ *    entries.  L2 group: g += (float)wd * p, as the other entry points.  Decoupled group:
+ *    p *= (float)(1 - lr * wd) first (product and difference in double), no wd term in g
+ *    (torch.optim.AdamW).  step_size = (float)(group_lr[group] / bc1).  The step counter, the
+ *    clip coefficient, the skip flag and the average are global.  A row whose group is outside
+ *    [0, n_groups) is left untouched (its average included) and reads no table.  With one L2
+ *    group the result is bit for bit that of the matching entry point above.
+ *    n_groups < 1 or a null table: E2EP_EINVAL. */
+int e2ep_adam_step_groups(const int *chunks, int n_chunks, const long long *offsets,
+                          const long long *grad_ptrs, const float *grad_flat, float *param,
+                          float *exp_avg, float *exp_avg_sq, float *step, const double *group_lr,
+                          const double *group_wd, const int *group_flags, int n_groups,
+                          double beta1, double beta2, double eps, float grad_scale,
+                          const float *clip_coef, const int *skip, int *stepped, float *ema,
+                          long long *ema_updates, double ema_decay, int ema_warmup,
+                          void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Training losses (fp32; fixed-order reductions; every scalar stays on the device):
