@@ -5,6 +5,7 @@
 // a two-consumer activation and the step's random draws (dropout seeds, drop-connect, target
 // noise) in one launch.
 #include "common.h"
+#include "mix64.h"
 
 namespace e2ep {
 
@@ -70,15 +71,9 @@ __global__ void k_add_i64_multi(const long long *table, int n, long long v) {
 }
 
 // Counter-based step draws: value i of draw number `state[1]` is a splitmix64 hash of
-// (state[0], state[1], i); floats take the top 24 bits (uniform on [0, 1)), ints the top 31.
-// One block: every thread reads the counter before thread 0 advances it, so each launch (or
-// graph replay) draws fresh values.
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// (state[0], state[1], i) (mix64.h); floats take the top 24 bits (uniform on [0, 1)), ints the
+// top 31.  One block: every thread reads the counter before thread 0 advances it, so each
+// launch (or graph replay) draws fresh values.
 __global__ void __launch_bounds__(1024) k_rng_draw(long long *state, int nf, float *f, int ni,
                                                    int *iv) {
   const unsigned long long seed = (unsigned long long)state[0];

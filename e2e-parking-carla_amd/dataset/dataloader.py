@@ -11,7 +11,11 @@ MI355X path (optional config keys, absent from the reference's YAML):
                        serve batches with GpuFrameLoader — decode on the GPU, batches already
                        in HBM (dataset/frame_cache.py);
   frame_cache_resident: true   keep the whole cache in HBM;
-  num_workers: N       DataLoader / cache-build workers (default 8, the reference's value).
+  num_workers: N       DataLoader / cache-build workers (default 8, the reference's value);
+  augment_brightness / augment_contrast / augment_saturation / augment_noise /
+  augment_gray_p: S    photometric jitter of the *training* images inside the decode launch
+                       (e2ep_amd/augment.py PhotoAugment; needs frame_cache; all 0 = none);
+  augment_per_camera: true   every camera of a sample draws its own jitter.
 """
 import os
 import random
@@ -50,7 +54,17 @@ class ParkingDataModule(_Base):
                           num_workers=getattr(self.cfg, "num_workers", None) or 8,
                           pin_memory=True, worker_init_fn=seed_worker, drop_last=True)
 
-    def _cached_loader(self, dataset, split, shuffle):
+    def _augment(self):
+        """The PhotoAugment of the optional augment_* config keys, None when all are zero."""
+        from e2ep_amd.augment import PhotoAugment
+        aug = PhotoAugment(**{k: float(getattr(self.cfg, "augment_" + k, 0.) or 0.)
+                              for k in ("brightness", "contrast", "saturation", "noise",
+                                        "gray_p")},
+                           per_camera=bool(getattr(self.cfg, "augment_per_camera", True)),
+                           seed=42)
+        return aug if aug.active else None
+
+    def _cached_loader(self, dataset, split, shuffle, augment=None):
         """Under DDP every rank runs setup(): rank 0 alone (re)builds the cache when it is
         missing or was built from another dataset / config (frame_cache.cache_matches), the
         others wait for it by polling the file system (frame_cache.wait_for_cache: a build
@@ -75,15 +89,18 @@ class ParkingDataModule(_Base):
         return GpuFrameLoader(cache, self.cfg.batch_size, shuffle=shuffle, drop_last=True,
                               seed=42, resident=bool(getattr(self.cfg, "frame_cache_resident",
                                                              False)),
-                              rank=rank, world=world)
+                              rank=rank, world=world, augment=augment)
 
     def setup(self, stage=None):
         train_set = CarlaDataset(self.data_dir, 1, self.cfg)
         val_set = CarlaDataset(self.data_dir, 0, self.cfg)
         if getattr(self.cfg, "frame_cache", None):
-            self.train_loader = self._cached_loader(train_set, "train", True)
-            self.val_loader = self._cached_loader(val_set, "val", False)
+            self.train_loader = self._cached_loader(train_set, "train", True, self._augment())
+            self.val_loader = self._cached_loader(val_set, "val", False)  # never augmented
         else:
+            if self._augment() is not None:
+                raise ValueError("augment_* keys need frame_cache: the jitter runs in the GPU "
+                                 "frame decode, not in the CPU loader")
             self.train_loader = self._loader(train_set, True)
             self.val_loader = self._loader(val_set, False)
 

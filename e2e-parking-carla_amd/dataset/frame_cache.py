@@ -259,10 +259,16 @@ class GpuFrameLoader:
     target_point (B,3), ego_motion (B,1,3), gt_control (B,T), gt_acc / gt_steer (B,F),
     gt_reverse (B,F).  The camera rig (intrinsics / extrinsics) is constant per cache and
     stays on the host by default (rig_on_host), where the model's LSS plan cache keys on it
-    (model/bev_model.py plan()); every other tensor is on the device."""
+    (model/bev_model.py plan()); every other tensor is on the device.
+
+    augment: a PhotoAugment (e2ep_amd/augment.py) jitters the images inside the decode launch.
+    A frame's draws are keyed by its sample's index in the cache and self.epoch, so a sample's
+    augmented image is a function of (augment, epoch, sample index) alone, whatever the batch
+    size, shuffle order, resident or streamed mode, rank or world.  Depth, segmentation, the
+    rig and the labels are untouched; None is the plain decode."""
 
     def __init__(self, cache, batch_size, shuffle=True, drop_last=True, seed=0, device=None,
-                 resident=False, rank=0, world=1, prefetch=2, rig_on_host=True):
+                 resident=False, rank=0, world=1, prefetch=2, rig_on_host=True, augment=None):
         if not torch.cuda.is_available():
             from e2ep_amd import _lib
             raise _lib.E2EPError("GpuFrameLoader needs a HIP device")
@@ -274,6 +280,11 @@ class GpuFrameLoader:
         self.rank, self.world = rank, world
         self.prefetch = max(1, int(prefetch))
         self.rig_on_host = rig_on_host
+        if augment is not None:
+            from e2ep_amd.augment import PhotoAugment
+            if not isinstance(augment, PhotoAugment):
+                raise TypeError(f"GpuFrameLoader: augment is {type(augment)}, not a PhotoAugment")
+        self.augment = augment
         self.epoch = 0
         self._dev = None
         self._rig = {}
@@ -310,11 +321,16 @@ class GpuFrameLoader:
             self._dev = dev
         return self._dev
 
-    def _assemble(self, rgb, depth_rgb, bev, labels, B, src=None, src_frames=None):
+    def _assemble(self, rgb, depth_rgb, bev, labels, B, idx, epoch, src=None, src_frames=None):
+        """idx: the batch's sample indices in the cache (host), the augmentation's keys."""
         from e2ep_amd import decode
         C = self.cache.crop
+        aug = {}
+        if self.augment is not None:
+            aug = dict(augment=self.augment, frame_key=self.augment.frame_keys(idx, 4),
+                       epoch=epoch)
         image, depth = decode.decode_frames(rgb.view(-1, C, C, 3), depth_rgb.view(-1, C, C, 3),
-                                            src_frame=src_frames)
+                                            src_frame=src_frames, **aug)
         seg = decode.widen_rows(bev, src_row=src)
         ex, ki = self._rig_for(B)
         batch = {"image": image.view(B, 4, 3, C, C), "depth": depth.view(B, 4, C, C),
@@ -325,18 +341,20 @@ class GpuFrameLoader:
 
     def _iter_resident(self):
         dev = self.upload()
+        epoch = self.epoch
         for idx in self.batches():
             B = len(idx)
             frames = (idx[:, None] * 4 + torch.arange(4)).reshape(-1)
             didx = idx.to(self.device, non_blocking=True)
             labels = {k: dev[k].index_select(0, didx) for k in LABEL_FIELDS}
-            yield self._assemble(dev["rgb"], dev["depth_rgb"], dev["bev"], labels, B,
+            yield self._assemble(dev["rgb"], dev["depth_rgb"], dev["bev"], labels, B, idx, epoch,
                                  src=idx, src_frames=frames)
 
     def _iter_streamed(self):
         batches = self.batches()
         if not batches:
             return
+        epoch = self.epoch
         width = max(len(b) for b in batches)
         slots = []
         for _ in range(self.prefetch + 1):
@@ -370,6 +388,7 @@ class GpuFrameLoader:
         copy = torch.cuda.Stream(self.device)
         main = torch.cuda.current_stream(self.device)
         inflight = []  # (slot, event of its H2D copy), oldest first
+        order = iter(batches)  # the producer fills slots in this order
         try:
             while True:
                 item = ready.get()
@@ -378,6 +397,7 @@ class GpuFrameLoader:
                 if isinstance(item, BaseException):
                     raise item
                 s, B = item
+                idx = next(order)
                 with torch.cuda.stream(copy):
                     host = slots[s]
                     d = {k: v[:B].to(self.device, non_blocking=True) for k, v in host.items()}
@@ -393,7 +413,8 @@ class GpuFrameLoader:
                     e0.synchronize()
                     free.put(s0)
                 labels = {k: d[k] for k in LABEL_FIELDS}
-                yield self._assemble(d["rgb"], d["depth_rgb"], d["bev"], labels, B)
+                # the augmentation's key table is built here, on the caller's thread
+                yield self._assemble(d["rgb"], d["depth_rgb"], d["bev"], labels, B, idx, epoch)
         finally:
             stop.set()
             for s in range(len(slots)):

@@ -13,6 +13,12 @@ Optional MI355X keys (absent from reference configs, defaults shown):
                                 multiple of learning_rate (a parameter group of its own)
   no_decay_norm_bias: False     no weight decay on norm scales, biases (ndim <= 1) and pos_embed
   decoupled_weight_decay: False AdamW's p *= 1 - lr * wd in place of the L2 term
+  augment_brightness / augment_contrast / augment_saturation: 0.0   photometric jitter of the
+                                training images in the GPU frame decode (needs frame_cache): the
+                                factor is uniform on [1 - v, 1 + v], v in [0, 1]
+  augment_noise: 0.0            amplitude of uniform per-pixel noise on the [0, 1] image, <= 0.5
+  augment_gray_p: 0.0           probability that a frame is turned grey
+  augment_per_camera: True      every camera of a sample draws its own jitter
 """
 import os
 from datetime import datetime
@@ -44,6 +50,12 @@ class Configuration:
     backbone_lr_scale = 1.0
     no_decay_norm_bias = False
     decoupled_weight_decay = False
+    augment_brightness = 0.0
+    augment_contrast = 0.0
+    augment_saturation = 0.0
+    augment_noise = 0.0
+    augment_gray_p = 0.0
+    augment_per_camera = True
 
 
 for _k in _KEYS:
@@ -70,6 +82,9 @@ def get_cfg(cfg_yaml: dict) -> Configuration:
     cfg.backbone_lr_scale = float(section.get("backbone_lr_scale", 1.0))
     cfg.no_decay_norm_bias = bool(section.get("no_decay_norm_bias", False))
     cfg.decoupled_weight_decay = bool(section.get("decoupled_weight_decay", False))
+    for k in ("brightness", "contrast", "saturation", "noise", "gray_p"):
+        setattr(cfg, "augment_" + k, float(section.get("augment_" + k, 0.0)))
+    cfg.augment_per_camera = bool(section.get("augment_per_camera", True))
     return cfg
 
 

@@ -1029,9 +1029,29 @@ int e2ep_linear_bwd(const float *dy, int ldy, const float *x, int ldx, const flo
  *  - e2ep_widen_u8_i64: rows x row_len uint8 class ids -> int64, output row r reading
  *    source row src_row[r] (r when NULL); row_len % 4 == 0, src 4-byte and dst 16-byte
  *    aligned.
+ *  - e2ep_frame_gray_mean: sums [frames][3] int64 = the exact R, G, B byte sums of source
+ *    frame src_frame[f] of rgb (zeroed and accumulated by the call: integer partials and
+ *    integer atomics, so exact in any order) and mean [frames] fp32 =
+ *    float32((0.299 sumR + 0.587 sumG + 0.114 sumB) / (255 hw)), evaluated in float64 and
+ *    rounded once: the contrast pivot of the augmented decode.  hw % 4 == 0.
+ *  - e2ep_decode_frames_aug: e2ep_decode_frames with a photometric jitter of the image
+ *    between the / 255 and the normalisation (brightness, contrast about gray_mean[f],
+ *    saturation or full grey with probability gray_p, uniform noise; strengths B, C, S,
+ *    gray_p in [0, 1], noise in [0, 0.5]).  Every draw is a splitmix64 hash of base (=
+ *    mix64(seed ^ mix64(epoch)), the uint64 passed as its int64 bits), the frame's key
+ *    frame_key[f] and the pixel's index in its frame; the full statement is at the kernel
+ *    (csrc/decode.hip) and in tests/augment_ref.py.  All strengths 0 gives
+ *    e2ep_decode_frames' image bit for bit; depth is never touched.  rgb is required.
  * ------------------------------------------------------------------------------------- */
 int e2ep_decode_frames(const void *rgb, const void *depth_rgb, const long long *src_frame,
                        long long frames, int hw, float *image, double *depth, void *stream);
+int e2ep_frame_gray_mean(const void *rgb, const long long *src_frame, long long frames, int hw,
+                         long long *sums, float *mean, void *stream);
+int e2ep_decode_frames_aug(const void *rgb, const void *depth_rgb, const long long *src_frame,
+                           const long long *frame_key, long long frames, int hw,
+                           const float *gray_mean, long long base, float B, float C, float S,
+                           float noise, float gray_p, float *image, double *depth,
+                           void *stream);
 int e2ep_widen_u8_i64(const void *src, const long long *src_row, long long rows, int row_len,
                       long long *dst, void *stream);
 
