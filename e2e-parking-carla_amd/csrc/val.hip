@@ -26,6 +26,12 @@
 //       workgroup.
 //   k_depth_metrics_final  one workgroup: each camera's records added by image, then chunk,
 //       written out and added to the epoch's running buffer.
+//   k_rollout_rows  one wave per row 3f + k of each sample: the free-running decoder's token
+//       (ParkingModel.forward_rollout) against the ground-truth token and the teacher-forced
+//       argmax (k_ctrl_val_rows' scan), detokenised against gt_acc / gt_steer / gt_reverse; one
+//       record per row.
+//   k_rollout_final  one workgroup: per future frame four float64 sums and eleven counts, the
+//       samples added in index order, written out and added to the epoch's running buffer.
 // One documented difference from the reference: it takes the argmax of the fp32 softmax, this
 // file the argmax of the logits.  The two agree whenever the row's two largest logits are
 // exactly equal (both pick the first index) and whenever they are far enough apart that their
@@ -62,6 +68,37 @@ __device__ __forceinline__ float smooth_l1(float x, float y) {
   return d < 1.f ? 0.5f * d * d : d - 0.5f;
 }
 
+// the argmax token of one logits row in torch.argmax's order (argmax.h), by one wave: a strided
+// scan per lane, then an xor butterfly, so every lane returns the row's token
+__device__ __forceinline__ int row_argmax_token(const float *__restrict__ xr, int V, int lane) {
+  float best = -INFINITY;
+  int bi = 0x7fffffff;  // ranks below every real candidate of equal value
+  for (int v = lane; v < V; v += 64) {
+    const float a = xr[v];
+    if (argmax_beats(a, v, best, bi)) best = a, bi = v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (argmax_beats(ob, oi, best, bi)) best = ob, bi = oi;
+  }
+  return bi;
+}
+
+// detokenize_acc on a Python int: float64, rounded by np.float32 afterwards
+template <typename I>
+__device__ __forceinline__ float detok_acc(I tok, int valid_token) {
+  const double half = (double)valid_token / 2.0, a = (double)tok / half - 1.0;
+  return (float)((double)tok > half ? a : -a);
+}
+
+// detokenize_steer on an int64 tensor and a Python float: fp32 arithmetic
+template <typename I>
+__device__ __forceinline__ float detok_steer(I tok, int valid_token) {
+  return (float)tok / (float)((double)valid_token / 2.0) - 1.f;
+}
+
 // row_vals: [acc | steer | reverse | reverse valid], B * F floats each
 __global__ void __launch_bounds__(VAL_THREADS)
     k_ctrl_val_rows(const float *__restrict__ x, const float *__restrict__ gt_acc,
@@ -76,30 +113,12 @@ __global__ void __launch_bounds__(VAL_THREADS)
   const float *xr = x + ((long long)b * T + j) * V;
   const long long i = (long long)b * F + f;
   if (k < 2) {
-    float best = -INFINITY;
-    int bi = 0x7fffffff;  // ranks below every real candidate of equal value
-    for (int v = lane; v < V; v += 64) {
-      const float a = xr[v];
-      if (argmax_beats(a, v, best, bi)) best = a, bi = v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (argmax_beats(ob, oi, best, bi)) best = ob, bi = oi;
-    }
+    const int bi = row_argmax_token(xr, V, lane);
     if (lane == 0) {
-      float pred;
-      if (k == 0) {
-        // detokenize_acc on a Python int: float64, rounded by np.float32 afterwards
-        const double half = (double)valid_token / 2.0, a = (double)bi / half - 1.0;
-        pred = (float)((double)bi > half ? a : -a);
-        row_vals[i] = smooth_l1(pred, gt_acc[i]);
-      } else {
-        // detokenize_steer on an int64 tensor and a Python float: fp32 arithmetic
-        pred = (float)bi / (float)((double)valid_token / 2.0) - 1.f;
-        row_vals[n + i] = smooth_l1(pred, gt_steer[i]);
-      }
+      if (k == 0)
+        row_vals[i] = smooth_l1(detok_acc(bi, valid_token), gt_acc[i]);
+      else
+        row_vals[n + i] = smooth_l1(detok_steer(bi, valid_token), gt_steer[i]);
     }
     return;
   }
@@ -423,6 +442,114 @@ inline int dm_chunks(int H, int W, int down) {
   return cdiv((long long)(H / down) * (W / down), DM_CHUNK);
 }
 
+// ---- free-running rollout metrics -----------------------------------------------------------
+// Row (b, j), j = 3f + k, compares the decoder's own token p = seq[b][1 + j] with the ground
+// truth g = gt_control[b][1 + j] and the teacher-forced argmax a of logits[b][j].  Its record
+// in the workspace is three 8-byte words: two float64 terms and an int64 of flag bits.
+//   k = 0  |acc_s - gt_acc|, smooth_l1(acc_v, gt_acc): acc_s the signed acceleration, acc_v
+//          detokenize_acc's folded one (detok_acc)
+//   k = 1  |steer - gt_steer|, smooth_l1(steer, gt_steer)
+//   k = 2  0, 0
+// Each term in float64 from two fp32 values.  A token is compared or converted to a number; it
+// never forms an address.
+constexpr int RO_SUMS = 4, RO_COUNTS = 11, RO_REC = RO_SUMS + RO_COUNTS, RO_WORDS = 3;
+constexpr long long RO_HIT = 1, RO_AGREE = 2, RO_INVALID = 4, RO_REVERSE = 8;
+
+__device__ __forceinline__ double smooth_l1_f64(float x, float y) {
+  const double d = fabs((double)x - (double)y);
+  return d < 1.0 ? 0.5 * d * d : d - 0.5;
+}
+
+__global__ void __launch_bounds__(VAL_THREADS)
+    k_rollout_rows(const long long *__restrict__ seq, long long seq_stride,
+                   const float *__restrict__ logits, const long long *__restrict__ gt_control,
+                   const float *__restrict__ gt_acc, const float *__restrict__ gt_steer,
+                   const long long *__restrict__ gt_rev, int B, int F, int V, int valid_token,
+                   double *__restrict__ recs) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * VAL_WAVES + (threadIdx.x >> 6);
+  const int J = 3 * F, T = J + 2;
+  if (r >= (long long)B * J) return;
+  const int b = (int)(r / J), j = (int)(r - (long long)b * J), f = j / 3, k = j - f * 3;
+  const int a = logits ? row_argmax_token(logits + ((long long)b * T + j) * V, V, lane) : -1;
+  if (lane != 0) return;
+  const long long p = seq[(long long)b * seq_stride + 1 + j];
+  const long long g = gt_control[(long long)b * (T + 1) + 1 + j];
+  const long long i = (long long)b * F + f;
+  long long flags = (p == g ? RO_HIT : 0) | (logits && p == (long long)a ? RO_AGREE : 0) |
+                    (p > (long long)valid_token ? RO_INVALID : 0);
+  double v0 = 0., v1 = 0.;
+  const double half = (double)valid_token / 2.0;
+  if (k == 0) {
+    const float y = gt_acc[i], acc_s = (float)((double)p / half - 1.0);
+    v0 = fabs((double)acc_s - (double)y);
+    v1 = smooth_l1_f64(detok_acc(p, valid_token), y);
+  } else if (k == 1) {
+    const float y = gt_steer[i], steer = detok_steer(p, valid_token);
+    v0 = fabs((double)steer - (double)y);
+    v1 = smooth_l1_f64(steer, y);
+  } else {
+    const long long t = gt_rev[i];
+    const bool rev = (double)p > half;  // detokenize's rule
+    flags |= (t == 1 ? rev : (t == 0 && !rev)) ? RO_REVERSE : 0;
+  }
+  double *rec = recs + r * RO_WORDS;
+  rec[0] = v0;
+  rec[1] = v1;
+  reinterpret_cast<long long *>(rec)[2] = flags;
+}
+
+// one workgroup: thread (frame, entry) adds its quantity over the samples in index order,
+// writes out and adds it to running.  out / running: double sums[F][4] | int64 counts[F][11]
+// (| int64 batches)
+__global__ void __launch_bounds__(VAL_THREADS)
+    k_rollout_final(const double *__restrict__ recs, int B, int F, double *__restrict__ out,
+                    double *__restrict__ running) {
+  const int J = 3 * F;
+  const long long *words = reinterpret_cast<const long long *>(recs);
+  for (int idx = threadIdx.x; idx < F * RO_REC; idx += VAL_THREADS) {
+    const int f = idx / RO_REC, e = idx - f * RO_REC;
+    if (e < RO_SUMS) {
+      // e = 0, 1: the first term of rows k = 0, 1; e = 2, 3: the second
+      const int k = e & 1, w = e >> 1;
+      double v = 0.;
+      for (int b = 0; b < B; ++b) v += recs[((long long)b * J + 3 * f + k) * RO_WORDS + w];
+      out[f * RO_SUMS + e] = v;
+      if (running) running[f * RO_SUMS + e] += v;
+    } else {
+      const int c = e - RO_SUMS;
+      long long v = 0;
+      for (int b = 0; b < B; ++b) {
+        const long long *row = words + ((long long)b * J + 3 * f) * RO_WORDS + 2;
+        const long long f0 = row[0], f1 = row[RO_WORDS], f2 = row[2 * RO_WORDS];
+        long long hit;
+        if (c == 0) {
+          hit = 1;
+        } else if (c <= 3) {
+          hit = ((c == 1 ? f0 : c == 2 ? f1 : f2) & RO_HIT) != 0;
+        } else if (c == 4) {
+          hit = (f0 & f1 & f2 & RO_HIT) != 0;
+        } else if (c == 5) {
+          long long all = RO_HIT;
+          for (int j = 0; j < 3 * f + 3; ++j) all &= words[((long long)b * J + j) * RO_WORDS + 2];
+          hit = all != 0;
+        } else if (c == 6) {
+          hit = (f2 & RO_REVERSE) != 0;
+        } else if (c == 7) {
+          hit = ((f0 | f1 | f2) & RO_INVALID) != 0;
+        } else {
+          hit = ((c == 8 ? f0 : c == 9 ? f1 : f2) & RO_AGREE) != 0;
+        }
+        v += hit;
+      }
+      const int slot = F * RO_SUMS + f * RO_COUNTS + c;
+      reinterpret_cast<long long *>(out)[slot] = v;
+      if (running) reinterpret_cast<long long *>(running)[slot] += v;
+    }
+  }
+  if (threadIdx.x == 0 && running) reinterpret_cast<long long *>(running)[F * RO_REC] += 1;
+}
+
 }  // namespace e2ep
 
 using namespace e2ep;
@@ -520,6 +647,45 @@ int e2ep_control_val_fwd(const float *logits, const float *gt_acc, const float *
   hipLaunchKernelGGL(k_ctrl_val_final, dim3(1), dim3(VAL_THREADS), 0, as_stream(stream), row_vals,
                      n, out);
   return launch_status("e2ep_control_val_fwd");
+}
+
+size_t e2ep_rollout_metrics_workspace(int B, int F) {
+  if (B <= 0 || F <= 0) return 0;
+  return (size_t)B * 3 * F * RO_WORDS * sizeof(double);
+}
+
+int e2ep_rollout_metrics(const long long *seq, long long seq_stride, const float *logits,
+                         const long long *gt_control, const float *gt_acc, const float *gt_steer,
+                         const long long *gt_reverse, int B, int F, int vocab, int valid_token,
+                         void *out, void *running, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+  E2EP_REQUIRE(seq && gt_control && gt_acc && gt_steer && gt_reverse && out && workspace,
+               E2EP_EINVAL, "e2ep_rollout_metrics: null argument");
+  E2EP_REQUIRE(B >= 1 && F >= 1, E2EP_EINVAL, "e2ep_rollout_metrics: bad shape (B=%d F=%d)", B, F);
+  E2EP_REQUIRE(vocab >= 5 && valid_token >= 1, E2EP_EINVAL,
+               "e2ep_rollout_metrics: bad vocabulary (vocab=%d, at least 5; valid_token=%d)", vocab,
+               valid_token);
+  E2EP_REQUIRE((long long)B * F * 3 <= 0x7fffffffLL / 4, E2EP_ERANGE,
+               "e2ep_rollout_metrics: B * F = %lld rows exceed the grid", (long long)B * F);
+  E2EP_REQUIRE(seq_stride >= 1 + 3LL * F, E2EP_EINVAL,
+               "e2ep_rollout_metrics: seq row stride %lld < 1 + 3 F = %lld", seq_stride,
+               1 + 3LL * F);
+  E2EP_REQUIRE(workspace_bytes >= e2ep_rollout_metrics_workspace(B, F), E2EP_EINVAL,
+               "e2ep_rollout_metrics: workspace %zu < %zu bytes", workspace_bytes,
+               e2ep_rollout_metrics_workspace(B, F));
+  E2EP_REQUIRE(((uintptr_t)seq & 7) == 0 && ((uintptr_t)logits & 3) == 0 &&
+                   ((uintptr_t)gt_control & 7) == 0 && ((uintptr_t)gt_acc & 3) == 0 &&
+                   ((uintptr_t)gt_steer & 3) == 0 && ((uintptr_t)gt_reverse & 7) == 0 &&
+                   ((uintptr_t)out & 7) == 0 && ((uintptr_t)running & 7) == 0 &&
+                   ((uintptr_t)workspace & 7) == 0,
+               E2EP_EINVAL, "e2ep_rollout_metrics: misaligned buffer");
+  double *recs = static_cast<double *>(workspace);
+  hipLaunchKernelGGL(k_rollout_rows, dim3(cdiv((long long)B * F * 3, VAL_WAVES)),
+                     dim3(VAL_THREADS), 0, as_stream(stream), seq, seq_stride, logits, gt_control,
+                     gt_acc, gt_steer, gt_reverse, B, F, vocab, valid_token, recs);
+  hipLaunchKernelGGL(k_rollout_final, dim3(1), dim3(VAL_THREADS), 0, as_stream(stream), recs, B, F,
+                     static_cast<double *>(out), static_cast<double *>(running));
+  return launch_status("e2ep_rollout_metrics");
 }
 
 size_t e2ep_seg_confusion_workspace(int images, int HW) {

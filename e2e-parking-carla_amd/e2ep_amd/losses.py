@@ -1,8 +1,9 @@
 """The three training losses (reference loss/*.py) as autograd ops over the fused HIP loss
 kernels (csrc/loss.hip): two launches forward (rows/blocks -> one fixed-order final sum),
 one backward, no host synchronisation, no PyTorch arithmetic.  The nn.Module wrappers in
-loss/ keep the reference's classes and signatures.  control_val, seg_confusion and
-depth_metrics are the validation metrics (csrc/val.hip): forward only, two launches each."""
+loss/ keep the reference's classes and signatures.  control_val, seg_confusion, depth_metrics
+and rollout_metrics are the validation metrics (csrc/val.hip): forward only, two launches
+each."""
 import torch
 
 from . import _lib
@@ -284,3 +285,78 @@ def depth_metrics(prob, gt, d_bound, down, n_cams, running=None, maps=False):
                   _lib.ptr(running), _lib.ptr(pred_map), _lib.ptr(gt_map), _lib.ptr(cls),
                   _lib.ptr(ws), _lib.nbytes(ws), _lib.stream())
     return (out, pred_map, gt_map, cls) if maps else out
+
+
+ROLLOUT_SUMS, ROLLOUT_COUNTS = 4, 11  # per future frame: float64 sums and int64 counts
+
+
+def rollout_metrics_bytes(F, running=False):
+    """Bytes of rollout_metrics' `out` buffer for F future frames, or of a `running` buffer (the
+    same layout followed by the int64 batch counter)."""
+    return 8 * (ROLLOUT_SUMS + ROLLOUT_COUNTS) * int(F) + (8 if running else 0)
+
+
+def rollout_metrics(seq, pred, gt_control, gt_acc, gt_steer, gt_reverse, token_nums, running=None):
+    """What the free-running control decoder emits against the ground truth, per future frame,
+    in two launches (csrc/val.hip).  seq (B, >= 1 + 3 F) int64, BOS first, then the decoder's own
+    tokens (ParkingModel.forward_rollout; any row stride); pred (B, 3 F + 2, vocab) fp32, the
+    teacher-forced logits of the same batch, or None; gt_control (B, 3 F + 3) token ids; gt_acc
+    and gt_steer (B, F); gt_reverse (B, F) 0 / 1.  With p the decoded token, g the ground-truth
+    one, a the argmax of pred's row and half = (token_nums - 4) / 2, per frame over the samples:
+        sums    |acc_s - gt_acc|, |steer - gt_steer|, smooth_l1(acc_v, gt_acc),
+                smooth_l1(steer, gt_steer)
+        counts  samples, p == g for acc / steer / reverse, all three, every token up to this
+                frame, (p_rev > half) == (gt_reverse == 1), any p > token_nums - 4, p == a for
+                acc / steer / reverse (0 without pred)
+    acc_s = p / half - 1 is the signed acceleration the agent executes (detokenize's throttle -
+    brake, against the signed label), acc_v and steer are control_val's detokenisations, so the
+    last two sums compare with acc_steer_val_loss.  Returns `out`, a uint8 tensor of
+    rollout_metrics_bytes(F) bytes holding this call alone: float64 sums[F][4] | int64
+    counts[F][11] (ValStep.unpack_rollout reads it).  `running`, a zeroed uint8 tensor of
+    rollout_metrics_bytes(F, running=True) bytes, has every entry of `out` added to it and its
+    batch counter incremented.  No autograd, no host read."""
+    _dev(seq, running)
+    if seq.dim() != 2 or seq.dtype != torch.int64 or seq.shape[1] < 4 or (seq.shape[1] - 1) % 3 \
+            or (seq.shape[0] > 1 and seq.stride(0) < seq.shape[1]) or seq.stride(1) != 1:
+        raise _lib.E2EPError(f"rollout_metrics: seq must be (B, 1 + 3 F) int64 with unit column "
+                             f"stride, got {seq.dtype} {tuple(seq.shape)} strides {seq.stride()}")
+    B, F = seq.shape[0], (seq.shape[1] - 1) // 3
+    T = 3 * F + 2
+    if B < 1:
+        raise _lib.E2EPError("rollout_metrics: seq has no sample")
+    if pred is not None:
+        _dev(pred)
+        if pred.dim() != 3 or pred.dtype != torch.float32 or tuple(pred.shape[:2]) != (B, T):
+            raise _lib.E2EPError(f"rollout_metrics: pred must be (B, 3 F + 2, vocab) fp32 = "
+                                 f"({B}, {T}, vocab), got {pred.dtype} {tuple(pred.shape)}")
+    if tuple(gt_control.shape) != (B, T + 1):
+        raise _lib.E2EPError(f"rollout_metrics: gt_control {tuple(gt_control.shape)} vs seq "
+                             f"{tuple(seq.shape)} (expected {(B, T + 1)})")
+    for name, t in (("gt_acc", gt_acc), ("gt_steer", gt_steer), ("gt_reverse", gt_reverse)):
+        if tuple(t.shape) != (B, F):
+            raise _lib.E2EPError(f"rollout_metrics: {name} {tuple(t.shape)} vs seq "
+                                 f"{tuple(seq.shape)} (expected {(B, F)})")
+    token_nums = int(token_nums)
+    if token_nums < 5 or (pred is not None and pred.shape[2] != token_nums):
+        raise _lib.E2EPError(f"rollout_metrics: token_nums {token_nums} (at least 5, and pred's "
+                             "vocabulary)")
+    if running is not None and (running.dtype != torch.uint8 or not running.is_contiguous()
+                                or running.numel() != rollout_metrics_bytes(F, True)):
+        raise _lib.E2EPError(f"rollout_metrics: running must be {rollout_metrics_bytes(F, True)} "
+                             f"contiguous uint8 bytes for {F} frames")
+    dev = seq.device
+    with torch.no_grad():
+        seq = seq.detach()
+        pred = None if pred is None else pred.detach().contiguous()
+        gtc = _i64(gt_control.detach(), dev)
+        acc = gt_acc.detach().to(device=dev, dtype=torch.float32).contiguous()
+        steer = gt_steer.detach().to(device=dev, dtype=torch.float32).contiguous()
+        rev = _i64(gt_reverse.detach(), dev)
+        out = torch.empty(rollout_metrics_bytes(F), dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.call_raw("e2ep_rollout_metrics_workspace", B, F), dtype=torch.uint8,
+                         device=dev)
+        _lib.call("e2ep_rollout_metrics", _lib.ptr(seq), max(seq.stride(0), seq.shape[1]),
+                  _lib.ptr(pred), _lib.ptr(gtc), _lib.ptr(acc), _lib.ptr(steer), _lib.ptr(rev), B,
+                  F, token_nums, token_nums - 4, _lib.ptr(out), _lib.ptr(running), _lib.ptr(ws),
+                  _lib.nbytes(ws), _lib.stream())
+    return out

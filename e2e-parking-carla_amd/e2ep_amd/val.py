@@ -15,6 +15,8 @@ ModelCheckpoint(monitor='val_loss') selects checkpoints by.  ValStep runs
                                                  sums, matrix and batch counter on the device
     losses.depth_metrics                         with depth_metrics=True, after the depth loss:
                                                  two launches, the depth head per camera
+    forward_rollout, losses.rollout_metrics      with rollout=True: the forward also decodes
+                                                 from BOS; two launches score the tokens
 
 as one replayed HIP graph (graph=True) or the same calls eagerly (graph=False).  No call reads
 anything back; result() makes the epoch's one device-to-host copy.
@@ -47,6 +49,19 @@ in [z_t, z_t + step) while a bin's depth is its lower edge z_t, so a perfect arg
 depth_abs_err of about step / 2.  The sums live in a second packed buffer, packed_depth, which
 shares packed's allocation, copy, zeroing and all-reduce.
 
+Rollout metrics (rollout=True): control_val scores the decoder under teacher forcing, every
+position seeing the ground-truth tokens before it; the agent runs it from BOS on its own tokens
+(ParkingModel.predict).  The step then runs ParkingModel.forward_rollout, which decodes every
+control token of the sample beside the teacher-forced forward, and losses.rollout_metrics scores
+the tokens per future frame f: rollout_acc_l1 and rollout_steer_l1 (the mean |executed value -
+label|, the acceleration signed as the agent applies it), the share of samples whose acc /
+steer / reverse token is the ground truth's (rollout_*_token_acc), all three
+(rollout_frame_exact), every token up to and including f (rollout_prefix_exact: still on the
+teacher's path), the reverse decision (rollout_reverse_acc), a decoded BOS / EOS / PAD
+(rollout_invalid), and the share whose token is the teacher-forced argmax (rollout_tf_agree_*).
+rollout_acc_steer_val_loss is acc_steer_val_loss's formula on the free-running tokens.  The sums
+live in a third packed buffer, packed_rollout, behind the other two in the same allocation.
+
 ParkingTrainingModule.validation_step and ControlValLoss remain as the Lightning-compatible
 path; this module does not change them."""
 import numpy as np
@@ -66,6 +81,13 @@ _DEPTH = (("depth_bin_acc", 1, "c", False), ("depth_bin_within1", 2, "c", False)
           ("depth_abs_err", 0, "s", False), ("depth_rmse", 1, "s", True),
           ("depth_abs_rel", 2, "s", False), ("depth_exp_abs_err", 3, "s", False),
           ("depth_exp_rmse", 4, "s", True), ("depth_true_bin_prob", 5, "s", False))
+# finish_rollout's per-frame keys: (name, index of the numerator, 's'um or 'c'ount)
+_ROLLOUT = (("rollout_acc_l1", 0, "s"), ("rollout_steer_l1", 1, "s"),
+            ("rollout_acc_token_acc", 1, "c"), ("rollout_steer_token_acc", 2, "c"),
+            ("rollout_reverse_token_acc", 3, "c"), ("rollout_frame_exact", 4, "c"),
+            ("rollout_prefix_exact", 5, "c"), ("rollout_reverse_acc", 6, "c"),
+            ("rollout_invalid", 7, "c"), ("rollout_tf_agree_acc", 8, "c"),
+            ("rollout_tf_agree_steer", 9, "c"), ("rollout_tf_agree_reverse", 10, "c"))
 
 
 class ValStep:
@@ -77,11 +99,13 @@ class ValStep:
     `depth_metrics=True` adds the per-camera depth metrics (losses.depth_metrics) to the chain
     and to result(); `depth_maps=True` also keeps the last batch's argmax-depth, ground-truth
     and class maps at cell resolution in `self.depth_maps`.
+    `rollout=True` adds the free-running decode and its metrics (losses.rollout_metrics) to the
+    chain and to result(); `self.rollout_tokens` and `self.rollout_out` hold the last batch's.
     Constructing the object accumulates nothing: the warm-up runs and the capture leave the
     packed buffer zero."""
 
     def __init__(self, module, batch, noise=None, world=1, graph=True, warmup=2, confusion=True,
-                 depth_metrics=False, depth_maps=False):
+                 depth_metrics=False, depth_maps=False, rollout=False):
         p = next(module.parameters(), None)
         if p is None or not p.is_cuda:
             raise _lib.E2EPError("ValStep: the module must be on the HIP device (there is no "
@@ -99,19 +123,29 @@ class ValStep:
         if self._want_maps and not self.depth_metrics:
             raise _lib.E2EPError("ValStep: depth_maps=True needs depth_metrics=True")
         self.cams = int(self.batch["depth"].shape[1]) if self.depth_metrics else 0
+        self.rollout = bool(rollout)
+        self.frames = int(module.cfg.future_frame_nums) if self.rollout else 0
+        if self.rollout and module.cfg.tf_de_tgt_dim != 3 * self.frames + 3:
+            raise _lib.E2EPError(f"ValStep: rollout=True needs tf_de_tgt_dim = 3 * "
+                                 f"future_frame_nums + 3 = {3 * self.frames + 3} (BOS, the control "
+                                 f"triples, EOS, PAD), got {module.cfg.tf_de_tgt_dim}")
         n = _HEAD + 8 * self.C * self.C
         nd = losses.depth_metrics_bytes(self.cams, running=True) if self.depth_metrics else 0
-        # one allocation, so one fill zeroes and one copy reads both packed buffers
-        self._buf = torch.zeros(n + nd, dtype=torch.uint8, device=dev)
+        nr = losses.rollout_metrics_bytes(self.frames, running=True) if self.rollout else 0
+        # one allocation, so one fill zeroes and one copy reads every packed buffer
+        self._buf = torch.zeros(n + nd + nr, dtype=torch.uint8, device=dev)
         self.packed = self._buf[:n]
-        self.packed_depth = self._buf[n:] if self.depth_metrics else None
-        self._host = torch.zeros(n + nd, dtype=torch.uint8).pin_memory()
+        self.packed_depth = self._buf[n:n + nd] if self.depth_metrics else None
+        self.packed_rollout = self._buf[n + nd:] if self.rollout else None
+        self._host = torch.zeros(n + nd + nr, dtype=torch.uint8).pin_memory()
         self.val_loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.pred = None  # (pred_control, pred_segmentation, pred_depth) of the last batch
         self.values = None  # device scalars of the last batch, by KEYS[:4]
         self.conf = None  # (C, C) int64 of the last batch
         self.depth_out = None  # losses.depth_metrics' buffer of the last batch
         self.depth_maps = None  # (pred_map, gt_map, cls) of the last batch, with depth_maps=True
+        self.rollout_tokens = None  # (B, 1 + 3 F) int64 of the last batch, BOS first
+        self.rollout_out = None  # losses.rollout_metrics' buffer of the last batch
         self._rig = _rig_key(batch)
         self._graph = None
         self._plans = []
@@ -130,9 +164,17 @@ class ValStep:
         try:
             with torch.no_grad():
                 batch = self.batch
-                pc, ps, pd = mod.parking_model(batch, self.noise)
+                toks = ro = None
+                if self.rollout:
+                    pc, ps, pd, toks = mod.parking_model.forward_rollout(batch, self.noise)
+                else:
+                    pc, ps, pd = mod.parking_model(batch, self.noise)
                 ctrl = losses.control_val_out(pc, batch["gt_acc"], batch["gt_steer"],
                                               batch["gt_reverse"], mod.cfg.token_nums)
+                if self.rollout:
+                    ro = losses.rollout_metrics(toks, pc, batch["gt_control"], batch["gt_acc"],
+                                                batch["gt_steer"], batch["gt_reverse"],
+                                                mod.cfg.token_nums, running=self.packed_rollout)
                 seg = mod.segmentation_loss_func(ps.unsqueeze(1), batch["segmentation"])
                 depth = mod.depth_loss_func(pd, batch["depth"])
                 dm = None
@@ -152,6 +194,7 @@ class ValStep:
             if was_training:
                 mod.train()
         self.pred, self.conf = (pc, ps, pd), conf
+        self.rollout_tokens, self.rollout_out = toks, ro
         if self._want_maps:
             self.depth_out, self.depth_maps = dm[0], dm[1:]
         else:
@@ -199,7 +242,7 @@ class ValStep:
 
     def reset(self):
         """Start an epoch: zero the running sums, the confusion matrix and the counter (and the
-        depth metrics' packed buffer, which shares the allocation)."""
+        depth and rollout metrics' packed buffers, which share the allocation)."""
         self._buf.zero_()
 
     def _merge(self):
@@ -211,7 +254,15 @@ class ValStep:
     def _merge_all(self):
         """_merge for both packed buffers, (packed, packed_depth or None): the depth metrics'
         sums and counts ride behind the others in the same all-reduce."""
+        return self._merge_every()[:2]
+
+    def _merge_every(self):
+        """_merge for the three packed buffers, (packed, packed_depth or None, packed_rollout
+        or None): the rollout metrics' sums and counts ride behind the depth metrics'."""
         ns = self.cams * losses.DEPTH_SUMS  # float64 sums at the head of packed_depth
+        nrs = self.frames * losses.ROLLOUT_SUMS  # and of packed_rollout
+        n0, n1 = self.packed.numel(), self._buf.numel() - (self.packed_rollout.numel()
+                                                           if self.rollout else 0)
         if dist.get_backend() == "nccl":
             sums = self.packed[:_HEAD - 8].view(torch.float64)
             counts = self.packed[_HEAD - 8:].view(torch.int64)
@@ -219,6 +270,9 @@ class ValStep:
             if self.depth_metrics:
                 parts += [self.packed_depth[:8 * ns].view(torch.float64),
                           self.packed_depth[8 * ns:].view(torch.int64).to(torch.float64)]
+            if self.rollout:
+                parts += [self.packed_rollout[:8 * nrs].view(torch.float64),
+                          self.packed_rollout[8 * nrs:].view(torch.int64).to(torch.float64)]
             flat = torch.cat(parts)
             dist.all_reduce(flat)
             flat = flat.cpu()
@@ -226,13 +280,17 @@ class ValStep:
             self._host.copy_(self._buf, non_blocking=True)
             torch.cuda.current_stream().synchronize()
             host = self._host.numpy()
-            sums, batches, conf = self.unpack(host[:self.packed.numel()])
+            sums, batches, conf = self.unpack(host[:n0])
             counts = np.concatenate([[batches], conf.reshape(-1) if conf is not None else []])
             parts = [sums, counts.astype(np.float64)]
             if self.depth_metrics:
-                dsums, dcounts, dbatches = self.unpack_depth(host[self.packed.numel():])
+                dsums, dcounts, dbatches = self.unpack_depth(host[n0:n1])
                 parts += [dsums.reshape(-1), dcounts.reshape(-1).astype(np.float64),
                           np.asarray([dbatches], dtype=np.float64)]
+            if self.rollout:
+                rsums, rcounts, rbatches = self.unpack_rollout(host[n1:])
+                parts += [rsums.reshape(-1), rcounts.reshape(-1).astype(np.float64),
+                          np.asarray([rbatches], dtype=np.float64)]
             flat = torch.from_numpy(np.concatenate(parts))
             dist.all_reduce(flat)
         flat = flat.numpy()
@@ -240,26 +298,39 @@ class ValStep:
         conf = (np.rint(flat[n + 1:n + 1 + cells]).astype(np.int64).reshape(self.C, self.C)
                 if self.C else None)
         packed = self.pack(flat[:n], int(round(flat[n])), conf)
-        if not self.depth_metrics:
-            return packed, None
+        packed_depth = packed_rollout = None
         d = flat[n + 1 + cells:]
-        dcounts = np.rint(d[ns:]).astype(np.int64)
-        return packed, self.pack_depth(d[:ns].reshape(self.cams, -1),
-                                       dcounts[:-1].reshape(self.cams, -1), int(dcounts[-1]))
+        if self.depth_metrics:
+            nd = self.cams * (losses.DEPTH_SUMS + losses.DEPTH_COUNTS) + 1
+            dcounts = np.rint(d[ns:nd]).astype(np.int64)
+            packed_depth = self.pack_depth(d[:ns].reshape(self.cams, -1),
+                                           dcounts[:-1].reshape(self.cams, -1), int(dcounts[-1]))
+            d = d[nd:]
+        if self.rollout:
+            rcounts = np.rint(d[nrs:]).astype(np.int64)
+            packed_rollout = self.pack_rollout(d[:nrs].reshape(self.frames, -1),
+                                               rcounts[:-1].reshape(self.frames, -1),
+                                               int(rcounts[-1]))
+        return packed, packed_depth, packed_rollout
 
     def result(self):
         """The epoch so far: one device-to-host copy (after one all-reduce when world > 1),
-        then finish(), and with depth_metrics=True finish_depth() merged into the same dict."""
+        then finish(), and with depth_metrics=True finish_depth() and with rollout=True
+        finish_rollout() merged into the same dict."""
         if self.world > 1:
-            packed, packed_depth = self._merge_all()
+            packed, packed_depth, packed_rollout = self._merge_every()
         else:
             self._host.copy_(self._buf, non_blocking=True)
             torch.cuda.current_stream().synchronize()
             host = self._host.numpy().copy()
-            packed, packed_depth = host[:self.packed.numel()], host[self.packed.numel():]
+            n0 = self.packed.numel()
+            n1 = host.size - (self.packed_rollout.numel() if self.rollout else 0)
+            packed, packed_depth, packed_rollout = host[:n0], host[n0:n1], host[n1:]
         out = self.finish(packed)
         if self.depth_metrics:
             out.update(self.finish_depth(packed_depth))
+        if self.rollout:
+            out.update(self.finish_rollout(packed_rollout))
         return out
 
     # -- host arithmetic on the packed buffer ------------------------------------------------
@@ -357,4 +428,59 @@ class ValStep:
         out = {k: (int(v) if k == "depth_cells" else float(v))
                for k, v in ratios(total_s, counts.sum(0)).items()}
         out["depth_per_camera"] = ratios(sums, counts)
+        return out
+
+    @staticmethod
+    def pack_rollout(sums, counts, batches):
+        """The rollout metrics' packed buffer (uint8 array) from the (F, 4) float64 sums, the
+        (F, 11) int64 counts (losses.rollout_metrics' order) and the batch count."""
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        F = sums.shape[0] if sums.ndim == 2 else -1
+        if (F < 1 or sums.shape != (F, losses.ROLLOUT_SUMS)
+                or counts.shape != (F, losses.ROLLOUT_COUNTS)):
+            raise _lib.E2EPError(f"ValStep: rollout sums {sums.shape} and counts {counts.shape} "
+                                 f"are not (F, {losses.ROLLOUT_SUMS}) and "
+                                 f"(F, {losses.ROLLOUT_COUNTS})")
+        tail = np.asarray([batches], dtype=np.int64)
+        return np.concatenate([sums.reshape(-1).view(np.uint8), counts.reshape(-1).view(np.uint8),
+                               tail.view(np.uint8)])
+
+    @staticmethod
+    def unpack_rollout(packed_rollout):
+        """(sums float64 (F, 4), counts int64 (F, 11), batches int) of a rollout packed buffer;
+        of one batch's `rollout_out` (no counter behind it) batches is None."""
+        raw = np.ascontiguousarray(np.asarray(packed_rollout, dtype=np.uint8).reshape(-1))
+        per = losses.rollout_metrics_bytes(1)
+        F, rest = divmod(raw.size, per)
+        if F < 1 or rest not in (0, 8):
+            raise _lib.E2EPError(f"ValStep: {raw.size} bytes are no packed rollout-metrics buffer")
+        ns = 8 * F * losses.ROLLOUT_SUMS
+        sums = raw[:ns].view(np.float64).reshape(F, -1).copy()
+        counts = raw[ns:F * per].view(np.int64).reshape(F, -1).copy()
+        return sums, counts, (int(raw[F * per:].view(np.int64)[0]) if rest else None)
+
+    @staticmethod
+    def finish_rollout(packed_rollout):
+        """Epoch results of the rollout metrics from their packed buffer's bytes, on the host:
+        the twelve per-frame ratios of the module docstring as float64 arrays of length F (each
+        numerator over the frame's samples, NaN where there is none), `rollout_samples`, and
+        `rollout_acc_steer_val_loss`: the mean over every (sample, frame) of the acc SmoothL1
+        plus that of the steer one, acc_steer_val_loss's formula on the free-running tokens (the
+        frames' sums added in order)."""
+        sums, counts, _ = ValStep.unpack_rollout(packed_rollout)
+        samples = counts[:, 0].astype(np.float64)
+        out = {}
+        for key, i, kind in _ROLLOUT:
+            num = (sums if kind == "s" else counts)[:, i].astype(np.float64)
+            v = np.full(samples.shape, np.nan)
+            np.divide(num, samples, out=v, where=samples > 0)
+            out[key] = v
+        acc = steer = 0.0
+        for row in sums:
+            acc, steer = acc + row[2], steer + row[3]
+        n = float(samples.sum())
+        out["rollout_acc_steer_val_loss"] = (float(acc) / n + float(steer) / n if n
+                                             else float("nan"))
+        out["rollout_samples"] = int(counts[0, 0])
         return out

@@ -10,7 +10,7 @@ reproducible runs; by default it is drawn on the device exactly like the referen
 import torch
 from torch import nn
 
-from e2ep_amd import conv, lss, nn_ops, rng, segments, streams
+from e2ep_amd import _lib, conv, lss, nn_ops, rng, segments, streams
 from model.bev_encoder import BevEncoder
 from model.bev_model import BevModel
 from model.control_predict import ControlPredict
@@ -106,6 +106,29 @@ class ParkingModel(nn.Module):
             if self.training:
                 rng.end_step()
         return pred_control, pred_segmentation, pred_depth
+
+    def forward_rollout(self, data, noise=None, steps=None):
+        """forward() plus the free-running decode of the same sample: (pred_control,
+        pred_segmentation, pred_depth, rollout_tokens).  The three predictions are forward()'s;
+        rollout_tokens (B, 1 + steps) int64 is what predict()'s loop emits from BOS
+        (gt_control[:, :1]) when the decoder is fed its own tokens, BOS first: a view of the
+        decode's (B, tf_de_tgt_dim - 1) buffer, so its row stride is that width.  `steps`
+        defaults to 3 * future_frame_nums, every control token of the sample.  The decode runs
+        between the teacher-forced decoder and the join of the segmentation head's side stream.
+        Where ar_decode.eligible holds (fp32 linears, B <= 16, no hooks) it is the KV-cached
+        incremental decode; elsewhere predict_tokens runs its full pass per token, as for
+        predict(): the same tokens.  Eval and no_grad only (validation: e2ep_amd.val)."""
+        if self.training:
+            raise _lib.E2EPError("ParkingModel.forward_rollout: eval mode only (the rollout is a "
+                                 "validation metric; call .eval() first)")
+        steps = 3 * self.cfg.future_frame_nums if steps is None else int(steps)
+        with torch.no_grad():
+            (fuse_feature, pred_segmentation, pred_depth, _), br = self._encoder_async(data, noise)
+            gt = data["gt_control"].to(fuse_feature.device, non_blocking=True)
+            pred_control = self.control_predict(fuse_feature, gt)
+            rollout_tokens = self.control_predict.predict_tokens(fuse_feature, gt[:, :1], steps)
+            pred_segmentation = br.join(pred_segmentation)
+        return pred_control, pred_segmentation, pred_depth, rollout_tokens
 
     def predict(self, data, noise=None):
         (fuse_feature, pred_segmentation, pred_depth, bev_target), br = self._encoder_async(data, noise)

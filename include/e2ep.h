@@ -1181,6 +1181,36 @@ int e2ep_target_select(const float *state, const float *goal, int B, float *targ
  *    down and W are multiples of 16 / sizeof(gt element) and gt is 16-byte aligned, element by
  *    element otherwise: the same cells and values.  out, running and workspace 8-byte aligned;
  *    workspace: e2ep_depth_metrics_workspace(BN, N, H, W, down) bytes (0 for a bad shape).
+ *
+ *  - e2ep_rollout_metrics: what the free-running control decoder emits (ParkingModel.predict's
+ *    loop from BOS) against the ground truth and against the teacher-forced argmax, per future
+ *    frame.  seq [B][seq_stride] int64 with BOS at column 0 and the decoded tokens behind it
+ *    (seq_stride in elements, >= 1 + 3 F); logits [B][T][vocab] fp32 contiguous, T = 3 F + 2,
+ *    the teacher-forced prediction, or NULL (the agreement counts are then 0); gt_control
+ *    [B][T + 1] int64; gt_acc, gt_steer [B][F] fp32; gt_reverse [B][F] int64.  E2EP_EINVAL
+ *    unless B >= 1, F >= 1, vocab >= 5 and valid_token >= 1.  With half = valid_token / 2.0,
+ *    for frame f and k = 0, 1, 2 (acc, steer, reverse): p = seq[b][1 + 3f + k],
+ *    g = gt_control[b][1 + 3f + k], a = the argmax of logits[b][3f + k] in torch.argmax's
+ *    order (first index of the largest value, NaN first);
+ *      acc_s = (float)((double)p_acc / half - 1): the signed acceleration the agent executes
+ *              (detokenize's throttle - brake);
+ *      acc_v = e2ep_control_val_fwd's k = 0 value (folded at half), steer its k = 1 value;
+ *      smooth_l1(x, y): d = |(double)x - (double)y|, d < 1 ? 0.5 * d * d : d - 0.5.
+ *    out (overwritten, this call alone): double sums[F][4] | int64 counts[F][11], 120 F bytes,
+ *    each entry the sum over b = 0 .. B-1 in index order:
+ *      sums    |acc_s - gt_acc|, |steer - gt_steer| (float64 from the two fp32 values),
+ *              smooth_l1(acc_v, gt_acc), smooth_l1(steer, gt_steer)
+ *      counts  samples; p == g for acc, steer, reverse; all three; every token of frames
+ *              0 .. f equal to its g; (p_rev > half) == (gt_reverse == 1), a gt_reverse outside
+ *              {0, 1} counting as wrong; any of the three p > valid_token (a BOS / EOS / PAD
+ *              id); p == a for acc, steer, reverse
+ *    An invalid token still enters the sums with the value its id detokenises to.  running (or
+ *    NULL): the same layout followed by int64 batches, 120 F + 8 bytes; every entry of out is
+ *    added to it with one add and batches is incremented.  Zero it to start an epoch.  Two
+ *    launches: one wave per row writes a record to the workspace, then one workgroup adds
+ *    them; no atomics.  A token value is compared or converted to a number, never used as an
+ *    index.  seq, gt_control, gt_reverse, out, running and workspace 8-byte aligned;
+ *    workspace: e2ep_rollout_metrics_workspace(B, F) bytes (0 for a bad shape).
  * ------------------------------------------------------------------------------------- */
 size_t e2ep_control_val_workspace(int B, int F);
 int e2ep_control_val_fwd(const float *logits, const float *gt_acc, const float *gt_steer,
@@ -1202,6 +1232,12 @@ int e2ep_depth_metrics_f64(const float *prob, const double *gt, int BN, int N, i
                            int down, double lo, double step, double d0, double dstep, void *out,
                            void *running, float *pred_map, float *gt_map, int *cls_out,
                            void *workspace, size_t workspace_bytes, void *stream);
+size_t e2ep_rollout_metrics_workspace(int B, int F);
+int e2ep_rollout_metrics(const long long *seq, long long seq_stride, const float *logits,
+                         const long long *gt_control, const float *gt_acc, const float *gt_steer,
+                         const long long *gt_reverse, int B, int F, int vocab, int valid_token,
+                         void *out, void *running, void *workspace, size_t workspace_bytes,
+                         void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * HIP-graph surgery: replace every memset node of a captured (not yet instantiated)

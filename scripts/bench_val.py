@@ -16,6 +16,14 @@ settings are called in alternating blocks so clock and thermal drift hit them al
                    depth_metrics=True: two more launches after the depth loss; the feature's cost
                    per batch is valstep_graph_depth - valstep_graph of the same series
 
+    --rollout      instead of the above, three captured settings only: valstep_graph,
+                   valstep_graph_rollout (ValStep(rollout=True): the forward also decodes every
+                   control token from BOS through the KV-cached ar_decode, and two launches
+                   score the tokens) and valstep_graph_rollout_fullpass (the same with the decode
+                   cache off when the step is captured, ar_decode._DECODE_CACHE: the full
+                   decoder pass per token); the rollout's cost per batch is
+                   valstep_graph_rollout - valstep_graph of the same series
+
 A block is `--block` calls, synchronised once at its end; its figure is ms per call.  Per
 setting: the median over blocks and their spread (min, max).  Launches are not traced.  The
 e2ep launches of the metric chain are counted on one eager ValStep call (entry-point calls
@@ -23,7 +31,8 @@ times the kernels behind each, LAUNCHES below); the torch kernels ControlValLoss
 launch are an ASSUMED count read off loss/control_loss.py; the result line says so
 (launch_count_basis).
 
-    python scripts/bench_val.py [--blocks 12] [--block 10] [--depth-metrics] [--json out.json]
+    python scripts/bench_val.py [--blocks 12] [--block 10] [--depth-metrics | --rollout]
+                                [--json out.json]
 """
 import argparse
 import json
@@ -39,13 +48,92 @@ import torch  # noqa: E402
 # kernel launches behind one call of a metric entry point (csrc/val.hip, csrc/loss.hip)
 LAUNCHES = {"e2ep_control_val_fwd": 2, "e2ep_seg_confusion": 2, "e2ep_val_accumulate": 1,
             "e2ep_seg_ce_fwd": 2, "e2ep_depth_bce_fwd": 2, "e2ep_depth_bce_fwd_f64": 2,
-            "e2ep_depth_metrics": 2, "e2ep_depth_metrics_f64": 2}
+            "e2ep_depth_metrics": 2, "e2ep_depth_metrics_f64": 2, "e2ep_rollout_metrics": 2}
 # ControlValLoss.forward as torch kernels, assumed one per op: 3 softmax, 2 argmax, 1 float
 # cast, acc: gt, 2 x (div, sub), neg, where; steer: div, sub; 2 x smooth_l1 (+ 2 reshape
 # copies of the strided argmax results); 2 partial sums, stack, CE on the transposed pair
 # (a contiguous copy, log_softmax, nll_loss); acc + steer; then sum(d.values()): 0 + a and
 # three more adds
 ASSUMED_TORCH_KERNELS = 3 + 2 + 1 + 1 + 4 + 1 + 1 + 2 + 2 + 2 + 2 + 1 + 3 + 1 + 4
+
+
+def _setup(a):
+    from e2ep_amd import _lib, synthetic
+    from tool.config import default_cfg
+    from trainer.pl_trainer import ParkingTrainingModule
+
+    _lib.load()
+    dev = torch.device("cuda")
+    torch.manual_seed(1234)
+    mod = ParkingTrainingModule(default_cfg()).to(dev).eval()
+    host = synthetic.synthetic_batch(a.batch, seed=0)
+    data = {k: (v if k in ("intrinsics", "extrinsics") else v.to(dev)) for k, v in host.items()}
+    return mod, data, synthetic.target_noise(a.batch, seed=0).to(dev)
+
+
+def _stats(t):
+    t = np.asarray(t)
+    return {"median_ms": round(float(np.median(t)), 4), "min_ms": round(float(t.min()), 4),
+            "max_ms": round(float(t.max()), 4), "blocks_ms": [round(float(x), 4) for x in t]}
+
+
+def rollout(a):
+    """--rollout: the three captured settings in alternating blocks."""
+    from e2ep_amd import ar_decode
+    from e2ep_amd.val import ValStep
+    mod, data, noise = _setup(a)
+    steps = {"valstep_graph": ValStep(mod, data, noise=noise, graph=True, warmup=2)}
+    before = ar_decode.LAUNCHES[0]
+    steps["valstep_graph_rollout"] = ValStep(mod, data, noise=noise, graph=True, warmup=2,
+                                             rollout=True)
+    kv_launches = (ar_decode.LAUNCHES[0] - before) // 3  # two warm-up runs and the capture
+    ar_decode._DECODE_CACHE[0] = False  # the path is fixed when the step is captured
+    try:
+        steps["valstep_graph_rollout_fullpass"] = ValStep(mod, data, noise=noise, graph=True,
+                                                          warmup=2, rollout=True)
+    finally:
+        ar_decode._DECODE_CACHE[0] = True
+
+    def block(name):
+        v = steps[name]
+        t0 = time.perf_counter()
+        for _ in range(a.block):
+            v()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.block * 1e3
+
+    order = list(steps)
+    for n in order:
+        block(n)
+    for v in steps.values():
+        v.reset()
+    times = {n: [] for n in order}
+    for r in range(a.blocks):
+        for n in order[r % len(order):] + order[:r % len(order)]:  # rotate who goes first
+            times[n].append(block(n))
+    res = {"config": f"one validation batch (eval fwd + 4 losses + metrics), B={a.batch}, "
+                     "4x256^2, fp32, captured; ms per call, one figure per block",
+           "blocks_per_setting": a.blocks, "calls_per_block": a.block}
+    for n in order:
+        res[n] = _stats(times[n])
+        res[f"{n}_spread_ms"] = round(res[n]["max_ms"] - res[n]["min_ms"], 4)
+    base = res["valstep_graph"]["median_ms"]
+    res["rollout_cost_graph_ms"] = round(res["valstep_graph_rollout"]["median_ms"] - base, 4)
+    res["rollout_fullpass_cost_graph_ms"] = round(
+        res["valstep_graph_rollout_fullpass"]["median_ms"] - base, 4)
+    res["dec_launches_per_call"] = kv_launches
+    out = {n: v.result() for n, v in steps.items()}
+    res["batches_accumulated"] = [out[n]["batches"] for n in order]
+    res["val_loss_mean"] = [out[n]["val_loss"] for n in order]
+    kv, full = steps["valstep_graph_rollout"], steps["valstep_graph_rollout_fullpass"]
+    res["rollout_tokens_equal_fullpass"] = bool(torch.equal(kv.rollout_tokens, full.rollout_tokens))
+    res["rollout_metrics"] = {k: np.asarray(v).tolist() for k, v in out["valstep_graph_rollout"].items()
+                              if k.startswith("rollout_")}
+    print(json.dumps(res))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
 
 
 def main():
@@ -55,8 +143,12 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--depth-metrics", action="store_true",
                     help="add the two ValStep settings with depth_metrics=True")
+    ap.add_argument("--rollout", action="store_true",
+                    help="time valstep_graph against the two captured rollout=True settings only")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    if a.rollout:
+        return rollout(a)
     from e2ep_amd import _lib, synthetic
     from e2ep_amd.val import ValStep
     from tool.config import default_cfg
